@@ -1,7 +1,14 @@
 """Benchmark of the batched KF hot path on 1..N MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...        (multi-GPU, RCCL)
+
+A plain run sets up, warms up, times --steps launches and prints the JSON line.  --full adds, after
+the timed steps, the measurements that take runs of their own: the CPU baseline (`cpu_baseline`,
+~15 s) and the access-pattern ceiling probe (`roofline.pattern_ceiling`).  --dump-outputs DIR
+writes what the last timed step computed (trajectory, log-dets, final state; a fixed seeded
+sample of the filters, under 64 MB in all) as DIR/<name>.npy: the inputs are the same in every
+run, so two builds can be compared array by array.
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts the N ranks itself
 as child processes (torch.distributed.run, rendezvous on 127.0.0.1) before anything touches the
@@ -220,6 +227,10 @@ def cv_workload(cfg_id, cfg, args, rank, world, dev):
         xf, _ = kf.state()
         return xf, logdet[-1], (None if out[0] is None else traj)
 
+    def outputs():
+        xf, Pf = kf.state()
+        return {'traj': out[0], 'logdet': out[1], 'x_final': xf, 'P_final': Pf}
+
     def cpu():
         """The reference's per-filter step restated in C (oracle/cpu_kf.c: dense matrices in the
         reference's op order, OpenMP over filters) on this host's allotted cores for ~10 s of
@@ -400,7 +411,8 @@ def cv_workload(cfg_id, cfg, args, rank, world, dev):
     return dict(step=step, units=B * T, bytes=bytes_launch, bytes_per_unit=bytes_step, kernel=kernel,
                 traffic=load_traffic(cfg_id) if pmc else None, cpu=cpu,
                 valu=load_valu(cfg_id) if pmc else None,
-                gather=gather_payload, kf=kf, pcie=pcie, probe=probe, per_step=per_step, update_every=k,
+                gather=gather_payload, outputs=outputs, kf=kf, pcie=pcie, probe=probe, per_step=per_step,
+                update_every=k,
                 desc=f"BASELINE config {cfg_id}: {cfg['model']} ({2 * d}-state/{d}-meas), {cfg['dtype']}, "
                      f"B={B} filters/GPU, T={T}, dt={dt}, GPS update every {k} step(s)",
                 extra={'filters_per_gpu': B, 'time_steps_per_launch': T, 'update_every': k})
@@ -495,6 +507,10 @@ def ref15_workload(cfg, args, rank, world, dev):
         xf, _ = kf.state()
         return xf, logdet[-1], traj
 
+    def outputs():
+        xf, Pf = kf.state()
+        return {'traj': traj, 'logdet': logdet, 'x_final': xf, 'P_final': Pf}
+
     def cpu():
         """The reference's dense 15x15 event step restated in C (oracle/cpu_kf.c) on this host's
         allotted cores for ~10 s of these streams; plus the NumPy step (oracle/ref_kf.step15 +
@@ -568,7 +584,8 @@ def ref15_workload(cfg, args, rank, world, dev):
     return dict(step=step, units=B * T, bytes=bytes_launch, bytes_per_unit=bytes_event, probe=probe,
                 kernel='ref_events_lds_kernel',
                 traffic=load_traffic('ref15' if cfg['dtype'] == 'f64' else 'ref15f32', bytes_launch),
-                valu=load_valu('ref15') if cfg['dtype'] == 'f64' else None, cpu=cpu, gather=gather_payload, kf=kf,
+                valu=load_valu('ref15') if cfg['dtype'] == 'f64' else None, cpu=cpu, gather=gather_payload,
+                outputs=outputs, kf=kf,
                 desc=f'SURVEY 8f row 2: reference 15-state model (kf_workers.py:493-614), {cfg["dtype"]}, B={B} filters/GPU, '
                      f'T={T} events (IMU 200 Hz, GPS fix every {k}th event), dt={dt}',
                 extra={'filters_per_gpu': B, 'events_per_launch': T})
@@ -743,7 +760,7 @@ def log_workload(cfg, args, rank, world, dev):
     if cfg['parallel']:
         return dict(step=step, units=T, bytes=per_event * T, bytes_per_unit=per_event,
                     kernel=f'ref_chain_kernel<f64,{"M8" if ref8 else "M15"},stream> (map pass) + stream_* kernels',
-                    traffic=None, cpu=cpu, gather=None, kf=kf,
+                    traffic=None, cpu=cpu, gather=None, outputs=lambda: {'traj': traj, 'logdet': logdet}, kf=kf,
                     roofline_note='latency / issue-bound: the map pass runs its chunk length of events in '
                                   'sequence (one wave per SIMD), the covariance starts walk their windows of maps; '
                                   'the fraction is not the figure of merit',
@@ -753,7 +770,7 @@ def log_workload(cfg, args, rank, world, dev):
                     extra=dict(extra, stream_check=stream_check,
                                launch='hipGraph replay of the step' if getattr(args, 'graph', False) else 'eager'))
     return dict(step=step, units=T, bytes=per_event * T, bytes_per_unit=per_event, kernel='ref_chain_kernel',
-                traffic=None, cpu=cpu, gather=None, kf=kf,
+                traffic=None, cpu=cpu, gather=None, outputs=lambda: {'traj': traj, 'logdet': logdet}, kf=kf,
                 roofline_note='one filter: one wave whose per-event dependency chain bounds the rate (8 lanes, '
                               'one per axis chain); HBM is idle, so the fraction is not the figure of merit',
                 desc=desc + "synthetic log with the reference log's shape", extra=extra)
@@ -833,7 +850,7 @@ def dead_reckoning_workload(cfg, args, dev, stream, ingest_s):
     return dict(step=step, units=T, bytes=per_event * T, bytes_per_unit=per_event,
                 kernel='kf_events_select + kf_events_dt + kf_run_stream (ref_chain_kernel<f64,M8,stream> map pass and '
                        'stream_* kernels)',
-                traffic=None, cpu=cpu, gather=None, kf=kf,
+                traffic=None, cpu=cpu, gather=None, outputs=lambda: {'traj': traj}, kf=kf,
                 roofline_note='latency / issue-bound like config 1 (the map pass runs its chunk length of events in '
                               'sequence); the compaction\'s count is read back by the host once per step; bytes: '
                               'the select reads etype twice over the stream and reads + writes the kept events\' '
@@ -888,6 +905,14 @@ def sched_workload(cfg, args, rank, world, dev):
         x, _ = kf.state()
         last = (n_sel.long() - 1).clamp(min=0)
         return x, logdet.gather(0, last[None, :])[0], traj
+
+    def outputs():
+        """Rows past a filter's n_sel are never written: zero in the dump."""
+        x, _ = kf.state()
+        sel = torch.arange(T, device=dev)[:, None] < n_sel[None, :]
+        zero = lambda a, m: torch.where(m, a, torch.zeros((), dtype=a.dtype, device=dev))
+        return {'traj': zero(traj, sel[:, None, :]), 'logdet': zero(logdet, sel), 'sel_time': zero(sel_time, sel),
+                'n_sel': n_sel, 'x_final': x}
 
     def step():
         if rows:
@@ -944,7 +969,7 @@ def sched_workload(cfg, args, rank, world, dev):
     return dict(step=step, units=B * T, bytes=nbytes, bytes_per_unit=nbytes / (B * T),
                 kernel=kernel, traffic=load_traffic('sched') if measured_shape else None,
                 valu=load_valu('sched') if measured_shape else None,
-                cpu=cpu, gather=gather_payload, kf=kf,
+                cpu=cpu, gather=gather_payload, outputs=outputs, kf=kf,
                 roofline_note=f'{n_selected / (B * T):.3f} of the examined events are selected and applied (a '
                               f'full 15-state event each, its payload gathered per lane); the two passes move '
                               f'their actual HBM traffic (traffic, PMC: the gathers fetch whole 128-B lines) at '
@@ -1061,11 +1086,15 @@ def bf_workload(cfg, args, rank, world, dev):
         kf = kfmi.BatchedKF('ref15', width, 'f64', device=dev.index)
         launches = [(k, off) for k in range(1, n + 1) for off in range(0, math.comb(n, k), width)]
 
+        last = {}
+
         def step():
             for k, off in launches:
-                kf.eval_combos(ev, init, t0, t_end, k, combo_offset=off, logdets=False)
+                last['max_logdet'] = kf.eval_combos(ev, init, t0, t_end, k, combo_offset=off, logdets=False)[0]
         return dict(step=step, units=total_combos, unit='subsets/s', ref_steps=ref_steps, bytes=None,
                     bytes_per_unit=None, kernel='ref15_combo_kernel', traffic=None, cpu=cpu, gather=None, kf=kf,
+                    outputs=lambda: {'last_launch_max_logdet': last['max_logdet'][:math.comb(n, launches[-1][0])
+                                                                                  - launches[-1][1]]},
                     combos=total_combos,
                     desc=f'SURVEY 8f row 1: exhaustive brute-force search, n={n} candidate events (kf_workers.py:2311), '
                          f'all 2^{n}-1 subsets, reference 15-state model, f64, {len(launches)} kf_eval_combos launches '
@@ -1082,14 +1111,33 @@ def bf_workload(cfg, args, rank, world, dev):
                                         fixed_mask=c)
         return k, idx
 
+    last = {}
+
     def step():
         # R_threshold below every subset's score: every size of every class (no early exit)
         if world > 1:
-            kdist.search_winner(search_class, n, w, exhaustive=True)
+            last['won'] = kdist.search_winner(search_class, n, w, exhaustive=True)
         elif w == 0:
-            kf.search_combos(ev, init, t0, t_end, -1e30, exhaustive=True)
+            last['one'] = kf.search_combos(ev, init, t0, t_end, -1e30, exhaustive=True)
         else:
-            r15.class_search(search_class, n, w, mine, exhaustive=True)
+            last['classed'] = r15.class_search(search_class, n, w, mine, exhaustive=True)
+
+    def outputs():
+        """What the search's caller receives: the accepted size (0 = none) and the winner as a 0/1
+        row over the n candidates; one call also its acceptance count per size."""
+        out = {}
+        if 'one' in last:
+            k, idx, acc, _ = last['one']
+            out['accepted_per_size'] = acc
+        elif 'won' in last:
+            k, idx = last['won'] if last['won'] else (0, None)
+        else:
+            k, key = last['classed']
+            k = 0 if k is r15.NO_SIZE else k
+            idx = [i for i in range(n) if (r15.bitrev64(key) >> i) & 1] if k else None
+        out['k_found'] = np.array([k])
+        out['winner'] = np.array([1.0 if idx is not None and i in idx else 0.0 for i in range(n)])
+        return out
 
     def dist_check():
         """N > 1, after the timed region: the reference's search (not exhaustive: it stops at the
@@ -1177,7 +1225,8 @@ def bf_workload(cfg, args, rank, world, dev):
                 kernel=f'ref15_search_head_kernel (sizes 1..{K}) + ref15_search_cm/pm_kernel + '
                        f'ref15_search_end_kernel (sizes {k_end}..{m}) ({launches} launches per class search)',
                 traffic=load_traffic(cfg_id, lvl_bytes), valu=valu if world == 1 else None,
-                cpu=cpu, gather=None, dist_check=dist_check if world > 1 else None, kf=kf, combos=total_combos,
+                cpu=cpu, gather=None, outputs=outputs, dist_check=dist_check if world > 1 else None, kf=kf,
+                combos=total_combos,
                 roofline_note='fp64 VALU issue: wave64 VALU instructions of one search (rocprofv3 SQ_INSTS_VALU, '
                               'profiles/pmc_valu.json) / its time, against 1024 SIMDs x 2.4 GHz / 4 cycles; the '
                               'level buffers (each stored prefix filter written and read once) are the hbm entry',
@@ -1239,6 +1288,38 @@ def launch_check(world, rank):
     return seen
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: the arrays of one run together (the limit is 64 MB)
+
+
+def dump_outputs(root, arrays, rank=0, budget=DUMP_BYTES):
+    """--dump-outputs: each array of ``arrays`` (name -> device tensor, host array or None) as
+    root/<name>.npy (rank r > 0: root/<name>.rank<r>.npy), float32 where the run computed float32
+    and float64 otherwise.  Arrays that together exceed ``budget`` bytes are cut (all but those
+    under budget / 256, kept whole) along their longest axis to a sorted sample of its indices
+    drawn from SEED: the same sample in every run, and the same filters in every array of a run
+    (arrays with the same longest axis share the draw).
+    Returns name -> saved shape."""
+    os.makedirs(root, exist_ok=True)
+    arrays = {k: (a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float64)))
+              for k, a in arrays.items() if a is not None}
+    width = lambda a: 4 if a.dtype == torch.float32 else 8
+    size = {k: a.numel() * width(a) for k, a in arrays.items()}
+    small = sum(s for s in size.values() if s <= budget // 256)   # kept whole
+    frac = 1.0 if sum(size.values()) <= budget else (budget - small) / (sum(size.values()) - small)
+    saved = {}
+    for name, a in arrays.items():
+        if frac < 1.0 and size[name] > budget // 256:
+            axis = max(range(a.dim()), key=lambda i: a.shape[i])
+            length = a.shape[axis]
+            keep = np.sort(np.random.default_rng(SEED).choice(length, max(1, int(length * frac)), replace=False))
+            a = a.index_select(axis, torch.from_numpy(keep).to(a.device))
+        a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(root, f'{name}.npy' if rank == 0 else f'{name}.rank{rank}.npy'), a)
+        saved[name] = a.shape
+    return saved
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -1246,7 +1327,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=None, help='untimed steps (default 10; bf40: 1)')
     ap.add_argument('--config', default='3', choices=sorted(CONFIGS))
     ap.add_argument('--batch', type=int, default=None, help='override filters per GPU')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the secondary measurements (N=1): the CPU baseline '
+                         '(cpu_baseline) and the access-pattern ceiling probe (roofline.pattern_ceiling)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step computed as DIR/<name>.npy (float32 / '
+                         'float64; a fixed seeded sample of the filters when the arrays exceed 48 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--pcie', action='store_true', help='also report the PCIe-inclusive rate (cv configs, N=1)')
     ap.add_argument('--per-step', action='store_true',
                     help='cv configs, N=1: also time the per-step predict()/update() call shape')
@@ -1355,6 +1442,9 @@ def main():
 
     kf = w['kf']
     bad = int((kf.status() != 0).sum().item()) if not args.config.startswith('bf') else 0
+    if args.dump_outputs:
+        # before anything else reuses the step's buffers (the pattern probe stores into them)
+        dumped = dump_outputs(args.dump_outputs, w['outputs'](), rank)
     gather_ms = gather_info = dist_info = None
     if dist:
         from kfmi import dist as kdist
@@ -1440,7 +1530,7 @@ def main():
                 rec['roofline']['valu'] = w['valu']
             if w.get('roofline_note'):
                 rec['roofline']['note'] = w['roofline_note']
-            if world == 1 and w.get('probe') and args.ablate == 'none':
+            if args.full and world == 1 and w.get('probe') and args.ablate == 'none':
                 # the same access pattern without the filter arithmetic, on the same buffers, right
                 # after the timed region: the ceiling this box's HBM placement gives the pattern
                 pr = w['probe'](max(args.steps, 5))
@@ -1468,6 +1558,8 @@ def main():
         rec['ranks_seen'] = ranks_seen
         if cfg['opts']:
             rec['options'] = cfg['opts']
+        if args.dump_outputs:
+            rec['dumped_outputs'] = {k: list(v) for k, v in dumped.items()}
         from kfmi import _lib as _kl
         rec['build'] = _kl.build_info()
         if gather_ms is not None:
@@ -1475,7 +1567,7 @@ def main():
             rec['allgather'] = gather_info
         if dist_info is not None:
             rec['dist_search'] = dist_info
-        rec['cpu_baseline'] = w['cpu']() if (world == 1 and not args.no_cpu_baseline) else None
+        rec['cpu_baseline'] = w['cpu']() if (args.full and world == 1 and not args.no_cpu_baseline) else None
         if args.pcie and world == 1 and w.get('pcie'):
             rec['pcie_inclusive'] = w['pcie']()
         if args.per_step and world == 1 and w.get('per_step'):

@@ -36,6 +36,36 @@ def test_plan_rejects_zero_gpus():
         bench.launch_plan(0, {}, [])
 
 
+def test_dump_outputs_samples_the_same_filters_every_time(tmp_path):
+    """--dump-outputs: float32 stays float32, everything else is written as float64, None is left
+    out; arrays over the budget are cut along their longest axis to one seeded, sorted sample that
+    arrays of the same length share and that a second run repeats."""
+    import numpy as np
+    import torch
+    B = 5000
+    traj = torch.arange(4 * 3 * B, dtype=torch.float64).reshape(4, 3, B)
+    arrays = {'traj': traj, 'logdet': traj[:, 0].float(), 'n_sel': torch.arange(B, dtype=torch.int32),
+              'acc': np.arange(7, dtype=np.uint64), 'absent': None}
+    budget = 64 * 1024
+    a = bench.dump_outputs(str(tmp_path / 'a'), arrays, budget=budget)
+    b = bench.dump_outputs(str(tmp_path / 'b'), arrays, budget=budget)
+    assert a == b and sorted(a) == ['acc', 'logdet', 'n_sel', 'traj']
+    got = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in a}
+    assert got['traj'].dtype == got['n_sel'].dtype == got['acc'].dtype == np.float64
+    assert got['logdet'].dtype == np.float32
+    assert sum(v.nbytes for v in got.values()) <= budget
+    np.testing.assert_array_equal(got['acc'], np.arange(7.0))   # a small array is kept whole
+    keep = got['n_sel'].astype(np.int64)                       # the sampled filter indices themselves
+    assert 0 < len(keep) < B and (np.diff(keep) > 0).all()
+    np.testing.assert_array_equal(got['traj'], traj.numpy()[:, :, keep])
+    np.testing.assert_array_equal(got['logdet'], traj.numpy()[:, 0, keep].astype(np.float32))
+    for k in a:
+        np.testing.assert_array_equal(got[k], np.load(tmp_path / 'b' / f'{k}.npy'))
+    # under the budget nothing is cut
+    full = bench.dump_outputs(str(tmp_path / 'c'), {'traj': traj})
+    assert full == {'traj': (4, 3, B)}
+
+
 def _run(args, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env.update(env_extra or {})
@@ -70,6 +100,32 @@ def _bench_ranks(gpus, config, extra=()):
     assert rec['n_gpus'] == rec['ranks_seen'] == gpus
     assert rec['failed_filters'] == 0 and rec['value'] > 0
     return rec
+
+
+@pytest.mark.gpu
+def test_plain_run_stops_at_its_headline_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` runs K timed steps and none of the --full
+    measurements (no CPU baseline, no pattern probe); --dump-outputs writes the last step's
+    trajectory, log-dets and final state, small enough here to be whole: the trajectory's last row
+    is the final state, finite, and the log-dets are one per step and filter."""
+    import numpy as np
+    B, T = 2048, 256
+    cmd =[sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+           '--batch', str(B), '--dump-outputs', str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['ms_per_step'] > 0 and rec['failed_filters'] == 0
+    assert rec['cpu_baseline'] is None and 'pattern_ceiling' not in rec['roofline']
+    assert rec['value'] == pytest.approx(B * T / (rec['ms_per_step'] * 1e-3), rel=1e-9)
+    got = {n[:-4]: np.load(tmp_path / n) for n in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ['P_final', 'logdet', 'traj', 'x_final']
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    assert got['traj'].shape == (T, 6, B) and got['logdet'].shape == (T, B) and got['x_final'].shape == (6, B)
+    np.testing.assert_array_equal(got['traj'][-1], got['x_final'])
+    assert rec['dumped_outputs']['traj'] == [T, 6, B]
 
 
 def _check_allgather(rec, gpus):

@@ -135,24 +135,6 @@ def test_csv_reader_large_multithreaded(tmp_path):
     np.testing.assert_array_equal(c, v.T)
 
 
-def test_real_gps_log_first_fix_kat():
-    """On the reference's own gps_data.csv (only where the reference checkout exists; never
-    copied into this repository): the first valid index and first fix that
-    KF_SensorFusion.ipynb:1331 prints."""
-    path = '/root/reference/gps_data.csv'
-    if not os.path.exists(path):
-        pytest.skip('reference checkout not present')
-    cols = ingest.read_csv(path, 4)
-    lat_ok = ~np.isnan(cols[1])
-    assert int(np.argmax(lat_ok)) == 2735
-    rows = ref_ingest.load_data_from_csv(path)
-    u = ref_ingest.gps_to_modified_utm(rows)
-    assert (u[0]['easting'], u[0]['northing'], u[0]['zone_number'], u[0]['zone_letter'], u[0]['altitude']) == \
-        (0.0, 0.0, 19, 'T', -32.6)
-    assert u[0]['time'] == 1697739552.3362827
-    assert len(u) == 21871
-
-
 def test_compat_model_matrices_are_the_reference_model():
     """kfmi.kf_workers keeps the reference's model definitions for class_args callers."""
     from kfmi import kf_workers as kfw

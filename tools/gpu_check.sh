@@ -24,7 +24,7 @@ cd "$ROOT"
 rocm-smi --showproductname > "$OUT/device.txt" 2>&1 || true
 step pytest_gpu 900 python -u -m pytest tests -m gpu -q -x -p no:cacheprovider --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py "$@"
+step bench 600 python bench.py --full "$@"
 cd /tmp
 # the bench command itself under rocprof: its JSON line (bench_profiled.json) and the kernel
 # stats come from one process, so they see the same HBM placement

@@ -22,7 +22,7 @@ step() {
 }
 for c in $CONFIGS; do
   cd "$ROOT"
-  step "bench_$c" 600 python bench.py --config "$c"
+  step "bench_$c" 600 python bench.py --full --config "$c"
   tail -1 "$OUT/bench_$c.log" > "$OUT/bench_$c.json"
   cd /tmp
   step "rocprof_$c" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o kt -- \

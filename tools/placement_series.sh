@@ -9,7 +9,7 @@ cd "$ROOT"
 # the box's clocks and partition modes beside the series (read-only queries)
 (rocm-smi --showclocks; rocm-smi --showcomputepartition --showmemorypartition) > "$OUT/smi.txt" 2>&1 || true
 for i in $(seq 1 "$N"); do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/run_$i.log" 2>&1 || { echo "run $i failed"; tail -5 "$OUT/run_$i.log"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/run_$i.log" 2>&1 || { echo "run $i failed"; tail -5 "$OUT/run_$i.log"; exit 1; }
   grep '^{"metric"' "$OUT/run_$i.log" | tail -1 >> "$OUT/lines.jsonl"
   python3 -c "import json; r=json.loads(open('$OUT/lines.jsonl').read().splitlines()[-1]); print($i, round(r['ms_per_step'],3), round(r['roofline']['frac'],3), round(r['roofline']['pattern_ceiling']['frac'],3), round(r['roofline']['pattern_ceiling']['achieved']))" | tee -a "$OUT/summary.txt"
 done
