@@ -364,6 +364,35 @@ int kf_run_stream(kf_batch* handle, int T, const uint8_t* etype, const double* d
                   void* traj, void* cov, void* logdet, uint8_t* updated, int chunk, int warmup,
                   void* stream);
 
+/* Threshold sweep: ONE event stream under the handle's B adaptive gates in one launch.  KF_MODEL_REF15
+ * / KF_MODEL_REF8.  etype device [T] uint8, dt device [T] double, payload device [T][9] (handle
+ * dtype): the shapes kf_run_stream takes.  Every filter of the handle runs all T events from its
+ * own state in the handle, each event as kf_run_events' with gate != 0, filter f against
+ * thresholds[f] (device [B] double): the update is applied only when logdet(P_pred) >
+ * thresholds[f] (kf_workers.py:1023-1025); -inf always updates (the gate is not evaluated) and
+ * +inf or NaN never does.
+ * KF_EVENT_PREDICT events only predict; KF_EVENT_NONE events leave the filter unchanged and still
+ * write their records.  Records in kf_run_events' layouts, each of which may be NULL: traj device
+ * [T][6][B] (REF8: [T][3][B]), logdet device [T][B], updated device [T][B] uint8; n_updated
+ * device [B] int32 receives each filter's number of applied updates.  With ckpt_every > 0, row c
+ * of ckpt_x device [C][n][B] and ckpt_P device [C][27][B] (REF8: [C][15][B]), C = T / ckpt_every,
+ * receives every filter's state and block-packed covariance after event (c + 1) ckpt_every - 1,
+ * in the handle's layout, so kf_set_state from a row and a sweep over the events after it
+ * continue the run bit for bit; both must be non-NULL when C > 0 (ckpt_every = 0: none).  The
+ * end states and per-filter status (KF_ENOTSPD for a filter that failed, that filter only) go
+ * back to the handle.  T = 0 returns KF_OK and leaves the handle untouched.  Limits of the
+ * kernel's 32-bit buffer descriptors (KF_EINVAL beyond them, never wrapped): the stream,
+ * 9 T w < 4 GiB, and one span of state rows, 27 B w < 2 GiB (w = 8 for f64, 4 for f32); the
+ * records and checkpoints are addressed per event and have no limit of their own.  One wave
+ * carries 8 filters and pays an event's update when any of them applies it, so a sweep costs
+ * about what its most-updating threshold costs.  Asynchronous on `stream`.  Replaces the
+ * run_adaptive_threshold_kalman_filter calls (kf_workers.py:959-1058) that the experiment loop
+ * repeats per r_value and start point (:2298-2317): one sweep over the log, its checkpoints the
+ * warm starts. */
+int kf_run_sweep(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                 const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
+                 int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
+
 /* The checks of the handle's last kf_run_stream (synchronises `stream`): out[0] = 1 if the
  * chunked run's records stood (0: the sequential fallback ran), out[1] = 1 if a chunk filter
  * failed, out[2] = covariance seam gap, out[3] = state seam gap (final pass only; records from

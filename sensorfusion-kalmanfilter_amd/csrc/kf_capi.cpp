@@ -957,6 +957,48 @@ int kf_run_events_seq(kf_batch* h, int T, const uint8_t* etype, const double* dt
     return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold, nullptr, stream);
 }
 
+int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                 const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
+                 int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream) {
+    if (int rc = check_handle(h)) return rc;
+    if (!is_ref(h)) return fail(KF_EINVAL, "kf_run_sweep: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle");
+    if (T < 0) return fail(KF_EINVAL, "kf_run_sweep: T = %d < 0", T);
+    if (ckpt_every < 0) return fail(KF_EINVAL, "kf_run_sweep: ckpt_every = %d < 0", ckpt_every);
+    if (T == 0 || h->B == 0) return KF_OK;
+    if (!etype || !dt || !payload) return fail(KF_EINVAL, "kf_run_sweep: null etype/dt/payload stream");
+    if (!thresholds) return fail(KF_EINVAL, "kf_run_sweep: null thresholds");
+    if (ckpt_every > 0 && T >= ckpt_every && (!ckpt_x || !ckpt_P))
+        return fail(KF_EINVAL, "kf_run_sweep: null ckpt_x/ckpt_P with %d checkpoints to write", T / ckpt_every);
+    // the kernel's descriptors: the stream by byte range (32-bit), the state rows as one span
+    // whose offsets keep bit 31 free for dropped lanes; records and checkpoints per event
+    const uint64_t w = elem(h);
+    if (uint64_t(T) * 9u * w >= (uint64_t(1) << 32))
+        return fail(KF_EINVAL, "kf_run_sweep: T = %d events exceed the 4 GiB payload descriptor (9 T w)", T);
+    if (uint64_t(h->B) * 27u * w >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "kf_run_sweep: B = %lld filters exceed the 2 GiB state span (27 B w)", (long long)h->B);
+    kfmi::SweepArgs a{};
+    a.B = h->B;
+    a.T = T;
+    a.etype = etype;
+    a.dt = dt;
+    a.payload = payload;
+    a.thresholds = thresholds;
+    a.x = h->x;
+    a.P = h->P;
+    a.status = h->status;
+    a.traj = traj;
+    a.logdet = logdet;
+    a.updated = updated;
+    a.n_updated = n_updated;
+    a.ckpt_every = ckpt_every;
+    a.ckpt_x = ckpt_x;
+    a.ckpt_P = ckpt_P;
+    a.kc = h->kc;
+    hipError_t e = kfmi::launch_ref_sweep(h->model == KF_MODEL_REF15 ? 15 : 8, h->dtype == KF_F64, a,
+                                          static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? KF_OK : hip_fail(e, "kf_run_sweep");
+}
+
 int kf_run_stream(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, void* traj,
                   void* cov, void* logdet, uint8_t* updated, int chunk, int warmup, void* stream) {
     return run_stream_impl(h, T, etype, dt, payload, traj, cov, logdet, updated, chunk, warmup, 0, 0.0, stream);

@@ -100,6 +100,29 @@ struct RefArgs {
     StreamCheck* s_check;
 };
 
+// Threshold sweep (kf_run_sweep, kf_workers.py:959-1058 under the thresholds of :2298-2317): the
+// handle's B filters all run the ONE stream etype / dt / payload ([T], [T], [T][9]) from their own
+// start states, filter f gated by thresholds[f].
+struct SweepArgs {
+    int64_t B;
+    int T;
+    const uint8_t* etype;    // [T]
+    const double* dt;        // [T]
+    const void* payload;     // [T][9]
+    const double* thresholds;  // [B]
+    void* x;                 // [N][B]
+    void* P;                 // [NBLK][B]
+    int32_t* status;         // [B]
+    void* traj;              // [T][NTRAJ][B] or nullptr
+    void* logdet;            // [T][B] or nullptr
+    uint8_t* updated;        // [T][B] or nullptr
+    int32_t* n_updated;      // [B] applied updates per filter, or nullptr
+    int ckpt_every;          // > 0: row c of ckpt_x / ckpt_P is the filter after event (c + 1) ckpt_every - 1
+    void* ckpt_x;            // [T / ckpt_every][N][B]
+    void* ckpt_P;            // [T / ckpt_every][NBLK][B]
+    const RefConsts* kc;     // the handle's own noise constants (device), or nullptr: the reference's
+};
+
 // Time-parallel run of one filter over a long event stream (kf_run_stream): the state banks of
 // the three chunk passes and the check.  Bank layouts are the handle's ([N][B], [NBLK][B]).
 struct StreamCheck {
@@ -361,6 +384,8 @@ hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t 
 // the chain kernel in stream mode (a.s_len > 0); nv = 4: the map pass, four state variants per
 // filter sharing its covariance (state bank of 4 B columns)
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv = 1);
+// one stream under the handle's B thresholds (ref_sweep_kernel: 8 lanes per filter)
+hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream);
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream);
 hipError_t launch_ref15_combos(bool f64, const Ref15ComboArgs& a, hipStream_t stream);
 // child_major: one wave per (parent block, child event) instead of one lane per parent

@@ -1145,6 +1145,227 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
+// Threshold sweep (kf_run_sweep): ONE event stream [T] run by B gated filters that differ only in
+// their adaptive threshold (kf_workers.py:959-1058; the experiment loop's r_value draw,
+// :2298-2317) and their start state.  The chain kernel's layout, 8 lanes per filter and lane c on
+// axis chain c, so a wave carries 8 thresholds; every group reads the same stream entries (byte
+// range descriptors as in stream mode: the 8 groups' loads hit one cache line), and the event's
+// type and dt are wave-uniform.  Each event is the chain kernel's, term for term: predict,
+// GateBand::open against the group's own threshold, sel_update_nv, the aw lane's inert-state
+// reset, NaN poisoning per group.  The groups of a wave disagree about `applied`, so the wave
+// pays the update whenever one of its groups applies it: a sweep costs about what its
+// most-updating threshold costs.  Records in kf_run_events' layouts ([T][W][B], [T][B]), an
+// update count per filter, and the handle-layout state every ckpt_every events.
+// ------------------------------------------------------------------------------------
+#ifndef KF_SWEEP_DEPTH
+#define KF_SWEEP_DEPTH 4
+#endif
+constexpr int kSweepDepth = KF_SWEEP_DEPTH;  // input ring of ref_sweep_kernel
+constexpr int kSweepBlock = 64;              // one wave (8 thresholds) per workgroup: waves spread over the CUs
+
+template <typename T, class M, bool CUSTOM>
+__global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs a) {
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
+    const int64_t f = g / kGroup;
+    if (f >= a.B) return;  // whole groups leave together
+    const int c = static_cast<int>(g % kGroup);
+    const bool pva = c < M::NP;
+    const bool live = c < M::NP + M::NA;
+    const int ca = pva ? c : (live ? c - M::NP : 0);
+    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
+    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
+    int xi[3], pr[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;  // (tt tw ww) of the 3x3 packing
+        pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
+    }
+    uint32_t vx[3], vp[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vx[k] = xi[k] >= 0 ? uint32_t(xi[k]) * rb + off : kDropOffset;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vp[k] = pr[k] >= 0 ? uint32_t(pr[k]) * rb + off : kDropOffset;
+    const uint32_t v_tr = (xi[0] >= 0 && xi[0] < M::NTRAJ) ? uint32_t(xi[0]) * rb + off : kDropOffset;
+    const uint32_t v_ld = c == 0 ? off : kDropOffset;
+    const uint32_t v_up = c == 0 ? uint32_t(f) : kDropOffset;
+    const int ia = pva ? ca : M::imu_att(ca);              // GPS position / IMU attitude column
+    const int ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);  // IMU acceleration / rate column
+    T q[3] = {T(pva ? kQPos : kQAtt), T(pva ? kQVel : kQRate), T(pva ? kQAcc : 0.0)};
+    T Rimu[6] = {T(pva ? kRPos : kRAtt), T(0), T(0), T(pva ? kRVel : kRRate), T(0), T(pva ? kRAcc : 1.0)};
+    T Rgps = T(kRGps);
+    if constexpr (CUSTOM) {  // this lane's chain states (the inert third state of an aw lane keeps 0 / 1)
+        const RefConsts* kc = a.kc;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (xi[k] >= 0) {
+                q[k] = T(ro(kc)->q[xi[k]]);
+                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
+            }
+        if (pva) Rgps = T(ro(kc)->r_gps[ca]);
+    }
+
+    T x[1][3], P[6];
+    {
+        const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[0][k] = ldv(rx, vx[k], T(0));
+#pragma unroll
+        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+    }
+    int32_t st = a.status[f];
+    int32_t nup = 0;
+    // the group's threshold; NaN never opens the gate (every comparison with it is false), and
+    // -inf is "always update": the gate is not evaluated (a covariance that is not positive
+    // definite has no log-det to compare, and the reference's slogdet still passes -inf there)
+    const double thr_d = a.thresholds[f];
+    const T thr = T(thr_d);
+    const bool always = thr_d == -__builtin_inf();
+    GateBand<T> gate;
+    gate.init(thr_d);
+    const bool need_tr = a.traj != nullptr, need_ld = a.logdet != nullptr, need_up = a.updated != nullptr;
+
+    const uint32_t S = uint32_t(a.T);
+    const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
+    const auto r_pay = bytes_rsrc(a.payload, S * 9u * uint32_t(sizeof(T)));
+    auto load = [&](int t, ChainIn<T>& in) {
+        const uint32_t ue = uint32_t(t);
+        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue, 0, 0));
+        in.dt = ldv(r_dt, ue * 8u, 0.0);
+        in.va = ldv(r_pay, (ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T)), T(0));
+        in.vb = ldv(r_pay, (ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T)), T(0));
+    };
+    int ck_left = a.ckpt_every;  // events until the next checkpoint (wave-uniform)
+    int ck_row = 0;
+    auto step = [&](int t, const ChainIn<T>& in) {
+        // every lane of the wave loaded the same type and dt: scalars
+        const int type = wave_uniform(in.type);
+        const T dt = T(in.dt);
+        const T va = in.va, vb = in.vb;
+        bool applied = false;
+        if (type != 255) {
+            // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
+            const T c02 = pva ? T(0.5) * dt * dt : T(0);
+            const T c12 = pva ? dt : T(0);
+            {
+                const T xn0 = fmaT(c02, x[0][2], fmaT(dt, x[0][1], x[0][0]));
+                const T xn1 = fmaT(c12, x[0][2], x[0][1]);
+                x[0][0] = xn0;
+                x[0][1] = xn1;
+            }
+            T FP[3][3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
+                FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
+                FP[2][j] = P[tri<3>(2, j)];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = i; j < 3; ++j) {
+                    T s = FP[i][j];
+                    if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
+                    if (j == 1) s = fmaT(FP[i][2], c12, s);
+                    P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
+                }
+            applied = (type == kGps || type == kImu);
+            if (applied && !always) applied = gate.open(P, live, thr);
+            bool ok = true;
+            if (applied) {
+                if (type == kGps) {
+                    if (pva) {
+                        T zb[1][1];
+                        zb[0][0] = va;
+                        const T R[1] = {Rgps};
+                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
+                    }
+                } else {
+                    T zb[1][3];
+                    const T V = fmaT(vb, dt, x[0][1]);
+                    const T X = fmaT(V, dt, x[0][0]);
+                    zb[0][0] = pva ? X : va;
+                    zb[0][1] = pva ? V : vb;
+                    zb[0][2] = pva ? vb : T(0);
+                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
+                    if (!pva) {  // reset the inert state
+                        x[0][2] = T(0);
+                        P[5] = T(1);
+                    }
+                }
+            }
+            if (group_any(!ok)) {
+                st = kNotSpd;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) x[0][k] = quiet_nan<T>();
+#pragma unroll
+                for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
+            }
+        }
+        nup += applied ? 1 : 0;
+        // absent records: skipped by wave-uniform branches
+        if (need_tr) stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, x[0][0]);
+        if (need_ld) {
+            const T ld = group_sum(live ? chain_log_det(P) : T(0));
+            st = (ld == ld) ? st : kNotSpd;
+            stv(span_rsrc(a.logdet, t, rb, 1), v_ld, ld);
+        }
+        if (need_up)
+            __builtin_amdgcn_raw_buffer_store_b8(applied ? uint8_t(1) : uint8_t(0),
+                                                 span_rsrc(a.updated, t, uint32_t(a.B), 1), v_up, 0, 0);
+        if (ck_left > 0 && --ck_left == 0) {  // checkpoint row ck_row: the filter after this event
+            ck_left = a.ckpt_every;
+            const auto cx = span_rsrc(a.ckpt_x, int64_t(ck_row) * M::N, rb, M::N);
+            const auto cp = span_rsrc(a.ckpt_P, int64_t(ck_row) * M::NBLK, rb, M::NBLK);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) stv(cx, vx[k], x[0][k]);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) stv(cp, vp[k], P[k]);
+            ++ck_row;
+        }
+    };
+
+    // the chain kernel's input ring (kSweepDepth - 1 events ahead; loads past the end re-read
+    // the last event)
+    constexpr int D = kSweepDepth;
+    const int T_ = a.T;
+    auto load_c = [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); };
+    if (T_ > 0) {
+        ChainIn<T> buf[D];
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j) load_c(j, buf[j]);
+        __builtin_amdgcn_s_waitcnt(0);
+        int t = 0;
+        for (; t + D <= T_; t += D) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                load_c(t + j + D - 1, buf[(j + D - 1) % D]);
+                step(t + j, buf[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j)
+            if (t + j < T_) step(t + j, buf[j]);
+    }
+    {
+        const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) stv(rx, vx[k], x[0][k]);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) stv(rp, vp[k], P[k]);
+    }
+    {
+        const auto rs = span_rsrc(a.status, 0, uint32_t(a.B) * 4u, 1);
+        __builtin_amdgcn_raw_buffer_store_b32(uint32_t(st), rs, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
+        if (a.n_updated) {
+            const auto rn = span_rsrc(a.n_updated, 0, uint32_t(a.B) * 4u, 1);
+            __builtin_amdgcn_raw_buffer_store_b32(uint32_t(nup), rn, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // ONE gated filter (B = 1, the adaptive threshold, kf_workers.py:959-1058) whose gate blocks
 // most updates, on one wave: lane c + 8 j is chain c (the chain kernel's lane layout) of event
 // slot j.  Every event that applies an update runs as the chain kernel's event (its arithmetic,
@@ -4402,6 +4623,21 @@ hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t 
         } else {
             if (f64) ref_stream_t<double, M8, CUSTOM>(a, stream, nv);
             else ref_stream_t<float, M8, CUSTOM>(a, stream, nv);
+        }
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
+    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8)) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
+    KF_CUSTOM_DISPATCH(a.kc, {
+        if (model == 15) {
+            if (f64) ref_sweep_kernel<double, M15, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
+            else ref_sweep_kernel<float, M15, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
+        } else {
+            if (f64) ref_sweep_kernel<double, M8, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
+            else ref_sweep_kernel<float, M8, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
         }
     });
     return hipGetLastError();

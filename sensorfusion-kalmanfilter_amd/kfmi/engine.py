@@ -391,6 +391,38 @@ class BatchedKF:
                                        _ptr(up), int(chunk), int(warmup), self._stream()))
         return tr, ld, up, cv
 
+    def run_sweep(self, etype, dt, payload, thresholds, traj=True, logdet=True, updated=False, counts=True,
+                  checkpoint_every=0):
+        """ONE event stream under this handle's B adaptive gates in one launch (kf_run_sweep):
+        etype [T] uint8, dt [T] float64, payload [T, 9]; filter f runs every event from its own
+        state in the handle and updates only where logdet(P_pred) > thresholds[f] ([B] float64;
+        -inf always, +inf or NaN never).  Returns (traj [T, W, B], logdet [T, B], updated [T, B],
+        n_updated [B] int32, ckpt_x [C, n, B], ckpt_P [C, rows, B]) with None for outputs not
+        asked for; C = T // checkpoint_every, row c the filters after event (c + 1) *
+        checkpoint_every - 1 (set_state(ckpt_x[c], ckpt_P[c]) and a sweep over the events after
+        it continue the run bit for bit)."""
+        if self.model not in REF_MODELS:
+            raise ValueError('run_sweep needs a ref15 or ref8 handle')
+        T = int(etype.shape[0])
+        every = int(checkpoint_every)
+        if every < 0:
+            raise ValueError('checkpoint_every must be >= 0')
+        et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
+        dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
+        pay = self._dev(payload.reshape(T, 9), (T, 9), 'payload')
+        thr = self._dev(thresholds, (self.batch,), 'thresholds', torch.float64)
+        tr = self.empty(T, TRAJ_WIDTH[self.model], self.batch) if traj else None
+        ld = self.empty(T, self.batch) if logdet else None
+        up = torch.empty(T, self.batch, dtype=torch.uint8, device=self.device) if updated else None
+        nu = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if counts else None
+        C = T // every if every > 0 else 0
+        cx = self.empty(C, self.n, self.batch) if every > 0 else None
+        cP = self.empty(C, self.ntri, self.batch) if every > 0 else None
+        check(_lib.lib().kf_run_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tr), _ptr(ld),
+                                      _ptr(up), _ptr(nu), every, _ptr(cx) if C else None, _ptr(cP) if C else None,
+                                      self._stream()))
+        return tr, ld, up, nu, cx, cP
+
     def stream_check(self):
         """The checks of the last run_stream (kf_stream_check; synchronises the stream)."""
         out = (ctypes.c_double * 8)()

@@ -465,6 +465,17 @@ class KF_SensorFusion:
                                                           initial_pt, initial_state, print_output, self.dtype,
                                                           self.device, consts=self._consts())
 
+    def run_adaptive_threshold_sweep(self, thresholds, start_idx=None, end_idx=None, initial_pt=None,
+                                     initial_state=None, records=True, checkpoint_every=4096):
+        """run_adaptive_threshold_kalman_filter for every R_threshold of ``thresholds`` in one
+        launch (ref15.AdaptiveSweep): .result(i) is that call's return value, .warm_start(i,
+        end_idx) the (states[-1], P, previous_time) of its prefix up to end_idx."""
+        return ref15.run_adaptive_threshold_sweep(self.indexed_sensor_data, thresholds, start_idx=start_idx,
+                                                  end_idx=end_idx, initial_pt=initial_pt,
+                                                  initial_state=initial_state, dtype=self.dtype, device=self.device,
+                                                  consts=self._consts(), records=records,
+                                                  checkpoint_every=checkpoint_every)
+
     def run_no_update_kalman_filter(self, start_idx=None, end_idx=None, R_threshold=None, initial_pt=None,
                                     initial_state=None, print_output=False):
         return ref15.run_no_update_kalman_filter(self.indexed_sensor_data, start_idx, end_idx, R_threshold,

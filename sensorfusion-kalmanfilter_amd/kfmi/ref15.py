@@ -562,6 +562,179 @@ def run_adaptive_threshold_kalman_filter(events, start_idx=None, end_idx=None, R
     return states, logdets, from_blocks(Pb[:, 0]), prev, mtimes
 
 
+class AdaptiveSweep:
+    """run_adaptive_threshold_kalman_filter (kf_workers.py:959-1058) over ONE window under every
+    threshold of ``thresholds`` at once (kf_run_sweep: one launch, 8 thresholds per wave), as the
+    experiment loop draws them (:2298-2317).  ``events``: an ingested stream (or an event list
+    over one), whose window never leaves the device, or a plain event list.  The drivers' rules
+    are run_monotone_stream's and the list path's: the cold start is the first fix in the
+    window, a dt < 0 event is skipped without advancing the previous time (here a NONE event, so
+    array entry 1 + j is event start + j), and a leading NONE event records the initial state.
+    The sweep's arrays stay on the device.
+
+    ``thresholds`` / ``n_updates``: NumPy [B].  ``result(i)``: the 5-tuple the driver returns
+    for thresholds[i] (needs records=True).  ``warm_start(i, end_idx)``: (states[-1], P,
+    previous_time) of the driver over [start_idx, end_idx), from the checkpoint at or before
+    end_idx (every ``checkpoint_every`` array entries) and a one-filter sweep over the fewer than
+    checkpoint_every events after it."""
+
+    def __init__(self, events, thresholds, start_idx=None, end_idx=None, initial_pt=None, initial_state=None,
+                 dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096):
+        from .ingest import events_dt
+        self.thresholds = np.array(thresholds, dtype=np.float64).reshape(-1)
+        self.dtype, self.consts, self.records = dtype, consts, bool(records)
+        self.every = int(checkpoint_every)
+        self.n_updates = np.zeros(len(self.thresholds), np.int64)
+        self.empty = True  # a cold window without a fix: the driver returns None
+        B = len(self.thresholds)
+        ds = _device_stream(events)
+        n = len(ds) if ds is not None else len(events)
+        start_idx = 0 if start_idx is None or start_idx < 0 else int(start_idx)
+        end_idx = n if end_idx is None or end_idx > n else int(end_idx)
+        self.start_idx, self.end_idx = start_idx, end_idx
+        warm = initial_pt is not None and initial_state is not None
+        x0 = np.zeros(15)
+        if warm:
+            P = np.asarray(initial_pt, np.float64)
+            x0[0:6] = initial_state[1:7]
+            prev0 = float(initial_state[0])
+            start_off = start_idx
+        else:
+            P = _p0(consts)
+            if ds is not None:
+                hit = torch.nonzero(ds.etype[start_idx:end_idx] == GPS)
+                if hit.numel() == 0:
+                    return
+                start_off = start_idx + int(hit[0, 0])
+                x0[0:3] = ds.payload[start_off, 0:3].double().cpu().numpy()
+                prev0 = float(ds.t[start_off])
+            else:
+                cs = _cold_start(events, start_idx, end_idx)
+                if cs is None:
+                    return
+                x0, prev0, start_off = cs
+        self.empty = B == 0
+        self.cold, self.prev0, self.start_off = not warm, prev0, start_off
+        T = max(end_idx - start_off, 0)
+        self.dev = ds.t.device if ds is not None else torch.device('cuda', device)
+        dev = self.dev
+        tdt = torch.float64 if dtype == 'f64' else torch.float32
+        if ds is not None:
+            t = ds.t[start_off:start_off + T]
+            dt, et = events_dt(t, prev0, _lib.KF_DT_MONOTONE, ds.etype[start_off:start_off + T])
+            pay = ds.payload[start_off:start_off + T].to(tdt)
+            t_host = t.double().cpu().numpy()
+            keep = et.cpu().numpy() != NONE
+        else:
+            t_host = np.zeros(T)
+            keep = np.zeros(T, bool)
+            et_h = np.full(T, NONE, np.uint8)
+            dt_h = np.zeros(T)
+            pay_h = np.zeros((T, 9))
+            prev = prev0
+            for j, (_, stype, tj, sdata) in enumerate(events[start_off:end_idx]):
+                t_host[j] = tj
+                d = tj - prev
+                if d < 0:  # kf_workers.py:1013-1015: skipped, previous_time NOT advanced
+                    continue
+                keep[j] = True
+                et_h[j] = GPS if stype == 'GPS' else IMU
+                dt_h[j] = d
+                pay_h[j] = event_payload(stype, sdata)
+                prev = tj
+            et = torch.from_numpy(et_h).to(dev)
+            dt = torch.from_numpy(dt_h).to(dev)
+            pay = torch.from_numpy(pay_h).to(dev).to(tdt)
+        # a NONE event first records the initial state and logdet (states[0], logdets[0])
+        self._et = torch.cat([torch.full((1,), NONE, dtype=torch.uint8, device=dev), et])
+        self._dt = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev), dt])
+        self._pay = torch.cat([torch.zeros(1, 9, dtype=tdt, device=dev), pay])
+        self._t = np.concatenate([[prev0], t_host])
+        self._keep = np.concatenate([[True], keep])
+        # time of the last processed entry at or before each entry (the driver's previous_time)
+        last = np.maximum.accumulate(np.where(self._keep, np.arange(T + 1), 0))
+        self._prev = self._t[last]
+        self._x0 = torch.as_tensor(x0[:, None], dtype=tdt, device=dev)
+        self._P0 = torch.as_tensor(to_blocks(P)[:, None], dtype=tdt, device=dev)
+        self._kf1 = None
+        if self.empty:
+            return
+        kf = BatchedKF('ref15', B, dtype, device=dev.index or 0, params=_params(consts))
+        try:
+            kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
+            (self._traj, self._ld, self._up, nu, self._cx, self._cP) = kf.run_sweep(
+                self._et, self._dt, self._pay, torch.from_numpy(self.thresholds), traj=self.records,
+                logdet=self.records, updated=self.records, checkpoint_every=self.every)
+            self._x, self._Pb = kf.state()
+            self._status = kf.status()
+            self.n_updates = nu.cpu().numpy().astype(np.int64)
+        finally:
+            kf.close()
+
+    def close(self):
+        if getattr(self, '_kf1', None) is not None:
+            self._kf1.close()
+            self._kf1 = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def result(self, i):
+        """(states, logdets, P, previous_time, measurement_times) of
+        run_adaptive_threshold_kalman_filter(..., R_threshold=thresholds[i]) over the window, or
+        None where it returns None."""
+        if not self.records:
+            raise ValueError('AdaptiveSweep.result needs records=True')
+        if self.empty:
+            return None
+        keep = torch.from_numpy(self._keep).to(self.dev)
+        traj = self._traj[:, :, i][keep].double().cpu().numpy()
+        ld = self._ld[:, i][keep].double().cpu().numpy()
+        up = self._up[:, i].cpu().numpy().astype(bool) & self._keep
+        up[0] = False
+        mtimes = ([self.prev0] if self.cold else []) + self._t[up].tolist()
+        P = from_blocks(self._Pb[:, i].double().cpu().numpy())
+        return _stream_states(self._t[self._keep], traj), ld.tolist(), P, float(self._prev[-1]), mtimes
+
+    def warm_start(self, i, end_idx):
+        """(state, P, previous_time): states[-1] (a 7-tuple) and the 15x15 P that
+        run_adaptive_threshold_kalman_filter(start_idx, end_idx, R_threshold=thresholds[i])
+        returns, or None where it returns None (a cold window whose first fix is not before
+        end_idx).  The checkpoint at or before end_idx, then a one-filter sweep over the tail
+        (none for an empty tail); previous_time comes from the host's times and types, which do
+        not depend on the threshold."""
+        if self.empty:
+            return None
+        end_idx = self.end_idx if end_idx is None or end_idx > self.end_idx else int(end_idx)
+        if self.cold and self.start_off >= end_idx:
+            return None
+        n = 1 + max(end_idx - self.start_off, 0)  # array entries of the prefix (the leading NONE included)
+        c = n // self.every - 1 if self.every > 0 else -1
+        if c >= 0:
+            x, Pb, lo = self._cx[c][:, i:i + 1], self._cP[c][:, i:i + 1], (c + 1) * self.every
+        else:
+            x, Pb, lo = self._x0, self._P0, 0
+        if n > lo:
+            if self._kf1 is None:
+                self._kf1 = BatchedKF('ref15', 1, self.dtype, device=self.dev.index or 0, params=_params(self.consts))
+            kf = self._kf1
+            kf.set_state(x.contiguous(), Pb.contiguous())
+            kf.run_sweep(self._et[lo:n], self._dt[lo:n], self._pay[lo:n], self.thresholds[i:i + 1], traj=False,
+                         logdet=False, counts=False)
+            x, Pb = kf.state()
+        xs = x[:6, 0].double().cpu().numpy()
+        prev = float(self._prev[n - 1])
+        return (prev, *xs.tolist()), from_blocks(Pb[:, 0].double().cpu().numpy()), prev
+
+
+def run_adaptive_threshold_sweep(events, thresholds, **kw):
+    """The AdaptiveSweep of ``events`` under ``thresholds`` (its keyword arguments)."""
+    return AdaptiveSweep(events, thresholds, **kw)
+
+
 def run_kalman_filter(events, start_idx, end_idx, dtype='f64', device=0, consts=None):
     """kf_workers.py:738-824 on the GPU: x0 = 0, the reference's P0, the window's events from
     its first GPS fix on (that fix at dt = 0), no dt < 0 guard.  Returns (states,
