@@ -31,13 +31,13 @@
  * All functions return KF_OK (0) or a negative KF_E* code; kf_last_error() then
  * describes the failure (thread-local).  Launching entry points are asynchronous on
  * the given hipStream_t (NULL = the null stream) and never synchronise, so they can be
- * captured into a hipGraph.  Workspaces: kf_search_combos, kf_run_stream and
+ * captured into a hipGraph.  Workspaces: kf_search_combos, kf_search_windows, kf_run_stream and
  * kf_run_scheduled(_rec) keep a device workspace in the handle, allocated by the first call
  * that needs it and grown (hipMalloc; hipFree synchronises the device) only by a call that
  * needs more than every earlier one; every other launch allocates nothing.  Run such a call
  * once eagerly before capturing it: inside a capture nothing is allocated (kf_run_scheduled
- * then takes its fused kernel, kf_run_stream returns KF_EINVAL; kf_search_combos synchronises
- * and is never captured).  A workspace a capture used
+ * then takes its fused kernel, kf_run_stream returns KF_EINVAL; kf_search_combos and
+ * kf_search_windows synchronise and are never captured).  A workspace a capture used
  * is never freed before kf_free, so a graph stays valid after a later, larger eager call: each
  * such growth keeps the smaller buffer (retired) until kf_free or kf_release_retired, so a
  * handle that alternates captures with ever-larger eager calls holds all of them.
@@ -334,6 +334,23 @@ int kf_run_events_seq(kf_batch* handle, int T, const uint8_t* etype, const doubl
                       void* traj, void* cov, void* logdet, uint8_t* updated, int gate, double threshold,
                       void* stream);
 
+/* kf_run_events_seq with a gate per filter: the arguments, layouts and records are
+ * kf_run_events', and filter f applies an event's update only when logdet(P_pred) >
+ * thresholds[f] (device [B] double, caller-owned, valid until the launch has run), in
+ * kf_run_sweep's conventions: -inf always updates and does not evaluate the gate, +inf and NaN
+ * never update.  A column whose threshold is t computes, bit for bit, what kf_run_events_seq
+ * computes for it with the scalar gate t (gate = 0 for -inf): the kernels are the same
+ * (KF_OPT_EVENTS_KERNEL 0 - 3 choose among them as for kf_run_events; 4, the one-filter
+ * look-ahead kernel, is KF_EINVAL here).  So one call carries filters that always update
+ * (run_kalman_filter_full), gated filters (run_adaptive_threshold_kalman_filter) and filters that
+ * never update (run_no_update_kalman_filter) side by side, each on its own [T][B] column: the
+ * experiment loop's windows (kf_workers.py:2320-2345), every one with its own r_value, as one
+ * batch.  Every filter runs its events in sequence (no one-filter route through kf_run_stream).
+ * Asynchronous on `stream`; capturable. */
+int kf_run_events_gates(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        void* traj, void* cov, void* logdet, uint8_t* updated, const double* thresholds,
+                        void* stream);
+
 /* One filter over a long event stream, parallel over time: kf_run_events for a handle of ONE
  * filter (B = 1, here without a gate), with the same arguments, outputs and final state, computed as
  * chunks of `chunk` events run as filters of one launch (chunk <= 0: max(128, T / 2048)).
@@ -448,6 +465,31 @@ int kf_search_combos(kf_batch* handle, int n_events, const double* events, const
                      double prev_time, double target_end, double threshold, int k_max, int exhaustive,
                      int n_fixed, uint64_t fixed_mask, uint64_t* winner, int* k_found,
                      uint64_t* n_accepted, void* subset_max, void* stream);
+
+/* KF_MODEL_REF15: W independent searches (windows) in one launch and one synchronisation.  Window
+ * w's result is what kf_search_combos(handle, n_events[w], events[w], init[w], prev_time[w],
+ * target_end[w], threshold[w], min(k_max, n_events[w]), exhaustive = 0, n_fixed = 0, ...)
+ * returns: k_found[w] the smallest size with an accepted subset (0: none up to k_max), winner[w]
+ * the mask of the first accepted subset of that size in itertools.combinations order,
+ * n_accepted[w][k] the accepted counts for k <= k_found[w] and 0 past it (nullable).  All host
+ * arrays: n_events [W] (1 .. n_max), events [W][n_max][11] (rows past n_events[w] are not read),
+ * init [W][42], prev_time / target_end / threshold [W], winner [W], k_found [W], n_accepted
+ * [W][k_max + 1].  One lane per (window, subset) over the sizes 1 .. k_max at once, each subset
+ * run from its window's root with kf_search_combos' per-subset arithmetic; nothing is stored
+ * between sizes, so it is for the short searches of many windows (a window that reports
+ * k_found = 0 is the caller's to pass to kf_search_combos with a larger k_max).  Axis symmetry
+ * (KF_OPT_AXIS_SYM) is decided per call: the call runs axis-symmetric only if every window's
+ * init qualifies as kf_search_combos requires.  Limits (KF_EINVAL, never wrapped): W >= 1,
+ * 1 <= n_max <= 64, 1 <= k_max <= 8, and W x max_w sum_{k <= k_max} C(n_w, k) < 2^31.  The
+ * handle's batch size is not used.  The inputs, the per-window arguments and the counters live in
+ * a handle workspace grown on demand ("Workspaces" above).  The call synchronises `stream` (the
+ * results return through a mapped host buffer of the handle): inside a graph capture it returns
+ * KF_EINVAL.  Replaces the brute-force calls of the experiment loop's windows
+ * (kf_workers.py:2337-2345), one per start point and r_value. */
+int kf_search_windows(kf_batch* handle, int W, int n_max, const int32_t* n_events, const double* events,
+                      const double* init, const double* prev_time, const double* target_end,
+                      const double* threshold, int k_max, uint64_t* winner, int32_t* k_found,
+                      uint64_t* n_accepted, void* stream);
 
 /* How kf_search_combos would run with these arguments, without running it (no device work):
  * out[0] = 1 if axis-symmetric (KF_OPT_AXIS_SYM and init's axis blocks equal bit for bit),

@@ -75,6 +75,14 @@ struct kf_batch {
     uint64_t* search_host_dev;
     bool search_ctr_zero;            // the counters are zero for a search queued on search_ctr_stream
     hipStream_t search_ctr_stream;
+    // kf_search_windows: device workspace (per-window arguments, events, inits, counters) and the
+    // mapped host buffer its finish kernel writes the results to, both grown on demand
+    void* win_ws;
+    size_t win_ws_bytes;
+    bool win_ws_graph;               // never set (the call is not capturable); grow_ws' interface
+    uint64_t* win_host;
+    uint64_t* win_host_dev;
+    size_t win_host_words;
 };
 
 namespace {
@@ -610,6 +618,8 @@ int kf_free(kf_batch* h) {
     if (h->ws_evt) (void)hipEventDestroy(h->ws_evt);
     if (h->search_ws) (void)hipFree(h->search_ws);
     if (h->search_host) (void)hipHostFree(h->search_host);
+    if (h->win_ws) (void)hipFree(h->win_ws);
+    if (h->win_host) (void)hipHostFree(h->win_host);
     if (h->flag) (void)hipFree(h->flag);
     if (h->stream_ws) (void)hipFree(h->stream_ws);
     if (h->pend_u) (void)hipFree(h->pend_u);
@@ -841,8 +851,9 @@ namespace {
 // that kernel, for the stream fallback's device-side choice)
 int run_events_launch(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, void* traj,
                       void* cov, void* logdet, uint8_t* updated, int gate, double threshold, const int32_t* skip,
-                      void* stream, int forced = -1) {
+                      void* stream, int forced = -1, const double* thresholds = nullptr) {
     kfmi::RefArgs a = ref_args(h);
+    a.thresholds = thresholds;  // kf_run_events_gates: per-filter gates (gate / threshold unused)
     a.T = T;
     a.etype = etype;
     a.dt = dt;
@@ -955,6 +966,19 @@ int kf_run_events_seq(kf_batch* h, int T, const uint8_t* etype, const double* dt
     int rc = KF_OK;
     if (!check_events_args(h, T, etype, dt, payload, "kf_run_events_seq", &rc)) return rc;
     return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold, nullptr, stream);
+}
+
+int kf_run_events_gates(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        void* traj, void* cov, void* logdet, uint8_t* updated, const double* thresholds,
+                        void* stream) {
+    int rc = KF_OK;
+    if (!check_events_args(h, T, etype, dt, payload, "kf_run_events_gates", &rc)) return rc;
+    if (!thresholds) return fail(KF_EINVAL, "kf_run_events_gates: null thresholds");
+    if (opt(h, KF_OPT_EVENTS_KERNEL) == 4)
+        return fail(KF_EINVAL, "kf_run_events_gates: KF_OPT_EVENTS_KERNEL = 4 (the one-filter look-ahead kernel) "
+                               "has no per-filter gates; use 0 - 3");
+    return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, 0, 0.0, nullptr, stream, -1,
+                             thresholds);
 }
 
 int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
@@ -1599,6 +1623,126 @@ int kf_search_combos(kf_batch* h, int n_events, const double* events, const doub
     const int reported = !exhaustive && found ? found : last;
     if (n_accepted)
         for (int k = 0; k <= k_max; ++k) n_accepted[k] = k <= reported ? acc[k] : 0;
+    return KF_OK;
+}
+
+int kf_search_windows(kf_batch* h, int W, int n_max, const int32_t* n_events, const double* events,
+                      const double* init, const double* prev_time, const double* target_end,
+                      const double* threshold, int k_max, uint64_t* winner, int32_t* k_found, uint64_t* n_accepted,
+                      void* stream) {
+    const char* who = "kf_search_windows";
+    if (int rc = check_handle(h)) return rc;
+    if (!is_ref15(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 handle", who);
+    if (W < 1) return fail(KF_EINVAL, "%s: W = %d < 1", who, W);
+    if (n_max < 1 || n_max > kMaxComboEvents)
+        return fail(KF_EINVAL, "%s: n_max = %d outside [1, %d]", who, n_max, kMaxComboEvents);
+    if (k_max < 1 || k_max > kfmi::kSearchWindowsMaxK)
+        return fail(KF_EINVAL, "%s: k_max = %d outside [1, %d]", who, k_max, kfmi::kSearchWindowsMaxK);
+    if (!n_events || !events || !init || !prev_time || !target_end || !threshold)
+        return fail(KF_EINVAL, "%s: null n_events/events/init/prev_time/target_end/threshold", who);
+    if (!winner || !k_found) return fail(KF_EINVAL, "%s: null winner/k_found", who);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (capturing(st)) return fail(KF_EINVAL, "%s: not capturable (its results return to the host in the call)", who);
+    const uint64_t* binom = binom_table();
+    auto C = [&](int a, int b) { return binom[a * (kMaxComboEvents + 1) + b]; };
+    const size_t ev_stride = size_t(n_max) * 11;
+    uint64_t max_lanes = 0;
+    bool sym = axis_sym_consts(h);
+    for (int w = 0; w < W; ++w) {
+        const int n = n_events[w];
+        if (n < 1 || n > n_max) return fail(KF_EINVAL, "%s: n_events[%d] = %d outside [1, n_max = %d]", who, w, n, n_max);
+        const double* ev = events + size_t(w) * ev_stride;
+        for (int i = 0; i < n; ++i) {
+            const double ty = ev[i * 11 + 1];
+            if (ty != KF_EVENT_GPS && ty != KF_EVENT_IMU)
+                return fail(KF_EINVAL, "%s: window %d event %d has type %g (GPS=0 or IMU=1)", who, w, i, ty);
+        }
+        uint64_t lanes = 0;
+        for (int k = 1; k <= std::min(k_max, n); ++k) lanes += C(n, k);  // < 2^36: no overflow
+        max_lanes = std::max(max_lanes, lanes);
+        sym = sym && search_sym(h, init + size_t(w) * 42);
+    }
+    if (uint64_t(W) * max_lanes >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: W x the widest window's subsets = %d x %llu reaches 2^31; split the call or lower k_max",
+                    who, W, static_cast<unsigned long long>(max_lanes));
+    // workspace: per-window arguments | events [W][n_max][11] | inits [W][42] | counters [W][2][slots]
+    const size_t args_b = align256(sizeof(kfmi::Ref15WindowArgs) * size_t(W));
+    const size_t ev_b = align256(sizeof(double) * ev_stride * size_t(W));
+    const size_t init_b = align256(sizeof(double) * 42 * size_t(W));
+    const size_t ctr_b = align256(sizeof(uint64_t) * 2 * kfmi::kSearchWindowSlots * size_t(W));
+    const size_t need = args_b + ev_b + init_b + ctr_b;
+    if (!grow_ws(h, &h->win_ws, &h->win_ws_bytes, &h->win_ws_graph, need, st))
+        return fail(KF_ENOMEM, "%s: hipMalloc of %zu bytes of workspace failed", who, need);
+    const size_t words = size_t(W) * size_t(3 + k_max);
+    if (h->win_host_words < words) {
+        if (h->win_host) (void)hipHostFree(h->win_host);
+        h->win_host = h->win_host_dev = nullptr;
+        h->win_host_words = 0;
+        void* p = nullptr;
+        if (hipHostMalloc(&p, sizeof(uint64_t) * words, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(KF_ENOMEM, "%s: hipHostMalloc of the result buffer failed", who);
+        }
+        void* pd = nullptr;
+        if (hipHostGetDevicePointer(&pd, p, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(p);
+            return fail(KF_EHIP, "%s: no device address for the result buffer", who);
+        }
+        h->win_host = static_cast<uint64_t*>(p);
+        h->win_host_dev = static_cast<uint64_t*>(pd);
+        h->win_host_words = words;
+    }
+    char* dw = static_cast<char*>(h->win_ws);
+    const double* d_ev = reinterpret_cast<const double*>(dw + args_b);
+    const double* d_init = reinterpret_cast<const double*>(dw + args_b + ev_b);
+    uint64_t* d_ctr = reinterpret_cast<uint64_t*>(dw + args_b + ev_b + init_b);
+    std::vector<kfmi::Ref15WindowArgs> wa(static_cast<size_t>(W));
+    const bool f64 = h->dtype == KF_F64;
+    for (int w = 0; w < W; ++w) {
+        kfmi::Ref15WindowArgs& a = wa[size_t(w)];
+        a = kfmi::Ref15WindowArgs{};
+        a.ev = d_ev + size_t(w) * ev_stride;
+        a.init = d_init + size_t(w) * 42;
+        a.prev_time = prev_time[w];
+        a.target_end = target_end[w];
+        a.threshold = threshold[w];
+        kfmi::Ref15SearchArgs band{};
+        band.threshold = threshold[w];
+        kfmi::set_search_band(band, f64);
+        a.band_lo_m = band.band_lo_m;
+        a.band_hi_m = band.band_hi_m;
+        a.band_lo_e = band.band_lo_e;
+        a.band_hi_e = band.band_hi_e;
+        a.band_mode = band.band_mode;
+        a.n_events = n_events[w];
+        a.k = std::min(k_max, n_events[w]);
+        for (int k = 1; k <= a.k; ++k) a.n_child += C(a.n_events, k);
+        a.best = d_ctr + size_t(w) * 2 * kfmi::kSearchWindowSlots;
+        a.n_acc = a.best + kfmi::kSearchWindowSlots;
+    }
+    hipError_t e = hipMemcpyAsync(dw, wa.data(), sizeof(kfmi::Ref15WindowArgs) * size_t(W), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw + args_b, events, sizeof(double) * ev_stride * size_t(W), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw + args_b + ev_b, init, sizeof(double) * 42 * size_t(W), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, ctr_b, st);
+    if (e != hipSuccess) return hip_fail(e, "kf_search_windows: upload");
+    const uint64_t* d_binom = reinterpret_cast<const uint64_t*>(static_cast<char*>(h->ws) + kWsEvents);
+    const auto* d_args = reinterpret_cast<const kfmi::Ref15WindowArgs*>(dw);
+    // the grid's y extent holds 65535 windows: more go in further launches of the same kernel
+    for (int w0 = 0; w0 < W && e == hipSuccess; w0 += 65535)
+        e = kfmi::launch_ref15_search_windows(f64, sym, d_args + w0, std::min(65535, W - w0), max_lanes, n_max, k_max,
+                                              d_binom, h->kc, st);
+    if (e != hipSuccess) return hip_fail(e, "kf_search_windows: launch");
+    e = kfmi::launch_search_windows_finish(d_args, W, k_max, h->win_host_dev, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "kf_search_windows: results");
+    for (int w = 0; w < W; ++w) {
+        const uint64_t* r = h->win_host + size_t(w) * size_t(3 + k_max);
+        winner[w] = r[0];
+        k_found[w] = static_cast<int32_t>(r[1]);
+        if (n_accepted)
+            for (int k = 0; k <= k_max; ++k) n_accepted[size_t(w) * size_t(k_max + 1) + k] = r[2 + k];
+    }
     return KF_OK;
 }
 

@@ -78,6 +78,10 @@ struct RefArgs {
     uint8_t* updated;        // [T][B] 1 if the event's update was applied, or nullptr
     int gate;                // adaptive threshold (kf_workers.py:1023-1025): update only if
     double threshold;        //   logdet(P_pred) > threshold
+    // kf_run_events_gates (per-filter layout only): filter f's own threshold, in kf_run_sweep's
+    // conventions (-inf: always update, the gate is not evaluated; +inf / NaN: never update);
+    // nullptr: the scalar gate / threshold above
+    const double* thresholds;  // device [B]
     // Stream mode (kf_run_stream, chain kernel only): ONE event stream of s_len events, laid
     // out as a single filter's [S] / [S][9] / records [S][W] ...; filter f runs the events
     // (f % s_nchunks) * s_chunk + s_shift + t, t < T; events outside [0, S) are skipped and
@@ -287,6 +291,26 @@ struct Ref15SearchArgs {
     int k_end;               // the end launch (launch_ref15_search_end): sizes k .. k_end
 };
 
+// Many independent windows in one search (kf_search_windows): one of these per window in a device
+// array, read by the wave-uniform window index.  Window w holds every subset of at most k of its
+// n_events candidates, one lane each, in (size, colex rank) order, as the head launch of
+// kf_search_combos does for one window (n_fixed = 0, nothing stored).
+struct Ref15WindowArgs {
+    const double* ev;        // device [n_events][11]
+    const double* init;      // device [15 + 27]
+    double prev_time, target_end, threshold;
+    double band_lo_m, band_hi_m;  // set_search_band's acceptance band of `threshold`
+    int band_lo_e, band_hi_e, band_mode;
+    int n_events;
+    int k;                   // sizes 1 .. k (the call's k_max clamped to n_events)
+    int pad;
+    uint64_t n_child;        // sum_{i <= k} C(n_events, i): the window's lanes
+    uint64_t* best;          // device [kSearchWindowSlots]: per size, max over accepted subsets of bitrev(mask)
+    uint64_t* n_acc;         // device [kSearchWindowSlots]: per size, accepted subsets
+};
+constexpr int kSearchWindowSlots = 16;   // counters per window and kind (sizes 0 .. 8 used)
+constexpr int kSearchWindowsMaxK = 8;
+
 // T rows of a search node: the block-packed P (27) and the running max's mantissa; an
 // axis-symmetric search (Ref15SearchArgs::sym) keeps one pva block and one aw block (6 + 3) and
 // the mantissa; then 4 B of exponent, 8 B of time and 8 B of mask per node
@@ -400,6 +424,15 @@ void set_search_band(Ref15SearchArgs& a, bool f64);
 hipError_t launch_ref15_search_head(bool f64, const Ref15SearchArgs& a, hipStream_t stream);
 // levels a.k .. a.k_end of a search in one launch, each subset from its stored (a.k - 1)-prefix
 hipError_t launch_ref15_search_end(bool f64, const Ref15SearchArgs& a, hipStream_t stream);
+// kf_search_windows: windows wins[0 .. W) (W <= 65535 per launch), max_lanes = the widest window's
+// lanes, every window's sizes 1 .. k in one launch (grid (ceil(max_lanes / 64), W))
+hipError_t launch_ref15_search_windows(bool f64, bool sym, const Ref15WindowArgs* wins, int W, uint64_t max_lanes,
+                                       int n_max, int k_max, const uint64_t* binom, const RefConsts* kc,
+                                       hipStream_t stream);
+// the windows' counters turned into results in `host` (the device address of mapped host memory),
+// [W][2 + k_max + 1] uint64: winner mask, k_found, n_accepted[0 .. k_max]
+hipError_t launch_search_windows_finish(const Ref15WindowArgs* wins, int W, int k_max, uint64_t* host,
+                                        hipStream_t stream);
 // a search's counters[0 .. n) (n <= 256) copied to `host` (the device address of mapped host
 // memory), and zeroed with `zero` (the end of the search)
 hipError_t launch_search_finish(uint64_t* counters, uint64_t* host, int n, bool zero, hipStream_t stream);

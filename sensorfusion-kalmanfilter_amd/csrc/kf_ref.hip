@@ -386,7 +386,21 @@ struct Chains {
 // ------------------------------------------------------------------------------------
 // Per-filter event streams (kf_run_events).
 // ------------------------------------------------------------------------------------
-template <typename T, class M, bool CUSTOM>
+// GATES (kf_run_events_gates): filter f's update is gated by its own a.thresholds[f], in the
+// sweep's conventions (gate_of); the instantiations without it are kf_run_events' as before.
+template <typename T>
+struct FilterGate {
+    bool on;  // the gate is evaluated (false: every event updates)
+    T thr;
+};
+template <typename T>
+__device__ __forceinline__ FilterGate<T> gate_of(const double* thresholds, int64_t f) {
+    const double t = thresholds[f];
+    // -inf is "always update": the gate is not evaluated; +inf and NaN fail every comparison
+    return FilterGate<T>{t != -__builtin_inf(), T(t)};
+}
+
+template <typename T, class M, bool CUSTOM, bool GATES = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void ref_events_kernel(const RefArgs a) {
     const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (f >= a.B) return;
@@ -398,6 +412,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
     s.kc = a.kc;
     s.load(a.x, a.P, rb, off);
     int32_t st = a.status[f];
+    FilterGate<T> fg{false, T(0)};
+    if constexpr (GATES) fg = gate_of<T>(a.thresholds, f);
     const uint32_t rb_tr = a.traj ? rb : 0u, rb_ld = a.logdet ? rb : 0u, rb_cv = a.cov ? rb : 0u;
     struct In {
         int type;
@@ -414,7 +430,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         bool applied = false;
         if (in.type != 255) {
             bool ok = true;
-            applied = s.template event<false>(in.type, T(in.dt), in.pay, a.gate != 0, T(a.threshold), ok);
+            applied = s.template event<false>(in.type, T(in.dt), in.pay, GATES ? fg.on : a.gate != 0,
+                                              GATES ? fg.thr : T(a.threshold), ok);
             if (!ok) {
                 st = kNotSpd;
                 s.fill_nan();
@@ -467,7 +484,7 @@ struct LdsPayload {
     __device__ __forceinline__ T operator[](int i) const { return img[i * 64]; }
 };
 
-template <typename T, class M, bool COV, bool CUSTOM>
+template <typename T, class M, bool COV, bool CUSTOM, bool GATES = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void ref_events_lds_kernel(
     const RefArgs a) {
     constexpr int W = int(sizeof(T));
@@ -491,6 +508,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
     s.kc = a.kc;
     s.load(a.x, a.P, rb, off);
     int32_t st = f < a.B ? a.status[f] : 0;
+    FilterGate<T> fg{false, T(0)};  // loaded with the state, ahead of the drain below
+    if constexpr (GATES) fg = gate_of<T>(a.thresholds, f < a.B ? f : a.B - 1);
     const uint32_t rb_tr = a.traj ? rb : 0u, rb_ld = a.logdet ? rb : 0u, rb_cv = a.cov ? rb : 0u;
     const uint32_t rb_up = a.updated ? uint32_t(a.B) : 0u;
     // drain the state loads once: left pending into the loop, the waitcnt pass puts a wait for
@@ -531,7 +550,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         bool applied = false;
         if (type != 255) {
             bool ok = true;
-            applied = s.template event<false>(type, dt, pay, a.gate != 0, T(a.threshold), ok);
+            applied = s.template event<false>(type, dt, pay, GATES ? fg.on : a.gate != 0, GATES ? fg.thr : T(a.threshold),
+                                              ok);
             if (!ok) {
                 st = kNotSpd;
                 s.fill_nan();
@@ -755,9 +775,12 @@ struct ChainIn {
 // each variant's arithmetic is the single-state lane's, term for term.  Variant v's state is
 // column v * B + f of a state bank of NV * B columns (the covariance: column f), and its
 // trajectory records go to rows v * s_vstride.
-template <typename T, class M, bool STREAM, bool CUSTOM, int NV = 1>
+// GATES (kf_run_events_gates, per-filter layout): each 8-lane group gates its filter by its own
+// a.thresholds[f], its GateBand set from it as ref_sweep_kernel's groups do.
+template <typename T, class M, bool STREAM, bool CUSTOM, int NV = 1, bool GATES = false>
 __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
     static_assert(NV == 1 || STREAM, "state variants are a stream-mode feature");
+    static_assert(!GATES || (!STREAM && NV == 1), "per-filter gates are a per-filter-layout feature");
     if (a.skip && *a.skip) return;  // the sequential fallback of a stream run that passed its checks
     constexpr int LPF = chain_lanes<NV>();         // lanes per filter
     constexpr int NL = LPF == 2 * kGroup ? 2 : NV;  // variants this lane holds
@@ -840,7 +863,13 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
     int32_t st = a.status[f];
     const bool need_ld = a.logdet != nullptr;
     GateBand<T> gate;
-    if (a.gate) gate.init(a.threshold);
+    FilterGate<T> fg{false, T(0)};
+    if constexpr (GATES) {
+        fg = gate_of<T>(a.thresholds, f);
+        if (fg.on) gate.init(a.thresholds[f]);
+    } else {
+        if (a.gate) gate.init(a.threshold);
+    }
     constexpr bool kLdBatch = STREAM && NV == 4 && kStreamLdBatch;
     T bm = T(1);  // kLdBatch: the group's determinant product of event (t - t mod 8 + c)
     int bex = 0;
@@ -925,7 +954,11 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
                     P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
                 }
             applied = (type == kGps || type == kImu);
-            if (a.gate && applied) applied = gate.open(P, live, T(a.threshold));
+            if constexpr (GATES) {
+                if (fg.on && applied) applied = gate.open(P, live, fg.thr);
+            } else {
+                if (a.gate && applied) applied = gate.open(P, live, T(a.threshold));
+            }
             bool ok = true;
             if (applied) {
                 if (type == kGps) {
@@ -3345,9 +3378,10 @@ __device__ __forceinline__ const uint64_t* search_binom_lds(const Ref15SearchArg
     return sbinom;
 }
 
+// The body shared by the head launch (one search) and the many-window launch (one search per
+// blockIdx.y): the one-wave workgroup's lanes are subsets blockIdx.x * 64 + lane of search `a`.
 template <typename T, bool CUSTOM, bool SYM>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SYM ? KF_SEARCH_SYM_WAVES : 3))) void ref15_search_head_kernel(
-    const Ref15SearchArgs a) {
+__device__ __forceinline__ void search_head_lanes(const Ref15SearchArgs& a) {
     using Node = SearchNode<T, CUSTOM, SYM>;
     constexpr int RP = SYM ? M15::NP : 1, RA = SYM ? M15::NA : 1;
     const int n = a.n_events, K = a.k;
@@ -3450,6 +3484,71 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SYM ? KF_SEA
         if (__builtin_amdgcn_ballot_w64(live && k == kk) != 0)
             search_publish(a, kk, k == kk ? best : 0, k == kk ? cnt : 0);
     if (a.tail) search_publish(a, K + 1, best1, cnt1);
+}
+
+template <typename T, bool CUSTOM, bool SYM>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SYM ? KF_SEARCH_SYM_WAVES : 3))) void ref15_search_head_kernel(
+    const Ref15SearchArgs a) {
+    search_head_lanes<T, CUSTOM, SYM>(a);
+}
+
+// Many windows in one launch (kf_search_windows): workgroup (x, w) is wave x of window w's
+// search, sizes 1 .. wins[w].k with nothing fixed and nothing stored — the head launch's lanes for
+// that window, so every score is kf_search_combos'.  The window's arguments are read through the
+// constant address space by the wave-uniform blockIdx.y (scalar loads).  A workgroup past its
+// window's lanes leaves whole, ahead of the binomial fill's barrier.  Dynamic LDS: the binomials
+// of the widest (n, k) of the call.
+template <typename T, bool CUSTOM, bool SYM>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SYM ? KF_SEARCH_SYM_WAVES : 3))) void ref15_search_windows_kernel(
+    const Ref15WindowArgs* wins, const uint64_t* binom, const RefConsts* kc) {
+    const auto* w = ro(wins) + blockIdx.y;
+    if (uint64_t(blockIdx.x) * 64 >= w->n_child) return;
+    Ref15SearchArgs a;
+    a.n_events = w->n_events;
+    a.k = w->k;
+    a.shift = 0;
+    a.k_base = 0;
+    a.root_mask = 0;
+    a.ev_all = a.ev = w->ev;
+    a.n_child = w->n_child;
+    a.binom = binom;
+    a.init = w->init;
+    a.prev_time = w->prev_time;
+    a.target_end = w->target_end;
+    a.threshold = w->threshold;
+    a.band_lo_m = w->band_lo_m;
+    a.band_hi_m = w->band_hi_m;
+    a.band_lo_e = w->band_lo_e;
+    a.band_hi_e = w->band_hi_e;
+    a.band_mode = w->band_mode;
+    a.child = nullptr;
+    a.best = w->best;
+    a.n_acc = w->n_acc;
+    a.subset_max = nullptr;
+    a.tail = 0;
+    a.kc = kc;
+    search_head_lanes<T, CUSTOM, SYM>(a);
+}
+
+// kf_search_windows' results: thread w turns window w's counters into (winner, k_found,
+// n_accepted[0 .. k_max]) in the mapped host buffer, by kf_search_combos' rule for a search that
+// stops at the first accepted size (the call clears the counters before its launch).
+__global__ __launch_bounds__(256) void search_windows_finish_kernel(const Ref15WindowArgs* wins, int W, int k_max,
+                                                                    uint64_t* host) {
+    const int w = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (w < W) {
+        const uint64_t* best = wins[w].best;
+        const uint64_t* acc = wins[w].n_acc;
+        const int k = wins[w].k;
+        int found = 0;
+        for (int i = 1; i <= k && !found; ++i)
+            if (best[i]) found = i;
+        uint64_t* out = host + int64_t(w) * (3 + k_max);
+        out[0] = found ? __builtin_bitreverse64(best[found]) : 0;
+        out[1] = uint64_t(found);
+        for (int i = 0; i <= k_max; ++i) out[2 + i] = found && i <= found ? acc[i] : 0;
+    }
+    __threadfence_system();
 }
 
 // The end of the search, sizes a.k .. a.k_end (free sizes) in ONE launch, extension-major: a
@@ -4573,6 +4672,20 @@ hipError_t launch_ref15_scheduled(bool f64, const Ref15SchedArgs& a, hipStream_t
 namespace {
 template <typename T, class M, bool CUSTOM>
 void ref_events_t(const RefArgs& a, hipStream_t stream, int variant) {
+    if (a.thresholds) {  // kf_run_events_gates: the same three kernels with per-filter gates
+        if (variant == kEventsLds) {
+            const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+            if (a.cov) ref_events_lds_kernel<T, M, true, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
+            else ref_events_lds_kernel<T, M, false, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
+        } else if (variant == kEventsChain) {
+            const dim3 cgrid(static_cast<unsigned>((a.B * kGroup + kBlock - 1) / kBlock));
+            ref_chain_kernel<T, M, false, CUSTOM, 1, true><<<cgrid, kBlock, 0, stream>>>(a);
+        } else {
+            const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+            ref_events_kernel<T, M, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
+        }
+        return;
+    }
     if (variant == kEventsLds) {
         const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
         if (a.cov) ref_events_lds_kernel<T, M, true, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
@@ -4601,6 +4714,7 @@ void ref_stream_t(const RefArgs& a, hipStream_t stream, int nv) {
 
 hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t stream, int variant) {
     if (model != 15 && model != 8) return hipErrorInvalidValue;
+    if (a.thresholds && (variant == kEventsGated || a.s_len != 0)) return hipErrorInvalidValue;
     KF_CUSTOM_DISPATCH(a.kc, {
         if (model == 15) {
             if (f64) ref_events_t<double, M15, CUSTOM>(a, stream, variant);
@@ -4824,6 +4938,33 @@ hipError_t launch_ref15_search_end(bool f64, const Ref15SearchArgs& a, hipStream
             else ref15_search_end_kernel<float, CUSTOM, false><<<grid, 64, 0, stream>>>(a);
         }
     });
+    return hipGetLastError();
+}
+
+hipError_t launch_ref15_search_windows(bool f64, bool sym, const Ref15WindowArgs* wins, int W, uint64_t max_lanes,
+                                       int n_max, int k_max, const uint64_t* binom, const RefConsts* kc,
+                                       hipStream_t stream) {
+    if (W < 1 || W > 65535 || n_max < 1 || n_max > kMaxEvents || k_max < 1 || k_max > kSearchWindowsMaxK ||
+        max_lanes == 0 || max_lanes * uint64_t(W) >= (1ull << 31))  // kf_search_windows' documented limit
+        return hipErrorInvalidValue;
+    const dim3 grid(unsigned((max_lanes + 63) / 64), unsigned(W));
+    const size_t lds = search_binom_lds_bytes(n_max, k_max + 1);
+    KF_CUSTOM_DISPATCH(kc, {
+        if (sym) {
+            if (f64) ref15_search_windows_kernel<double, CUSTOM, true><<<grid, 64, lds, stream>>>(wins, binom, kc);
+            else ref15_search_windows_kernel<float, CUSTOM, true><<<grid, 64, lds, stream>>>(wins, binom, kc);
+        } else {
+            if (f64) ref15_search_windows_kernel<double, CUSTOM, false><<<grid, 64, lds, stream>>>(wins, binom, kc);
+            else ref15_search_windows_kernel<float, CUSTOM, false><<<grid, 64, lds, stream>>>(wins, binom, kc);
+        }
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_search_windows_finish(const Ref15WindowArgs* wins, int W, int k_max, uint64_t* host,
+                                        hipStream_t stream) {
+    if (W < 1 || k_max < 1 || k_max > kSearchWindowsMaxK) return hipErrorInvalidValue;
+    search_windows_finish_kernel<<<dim3(unsigned((W + 255) / 256)), 256, 0, stream>>>(wins, W, k_max, host);
     return hipGetLastError();
 }
 

@@ -370,6 +370,27 @@ class BatchedKF:
                  float(threshold) if gate else 0.0, self._stream()))
         return tr, ld, up, cv
 
+    def run_events_gates(self, etype, dt, payload, thresholds, traj=True, logdet=True, updated=False, cov=False):
+        """run_events(sequential=True) with a gate per filter (kf_run_events_gates): filter f
+        updates only where logdet(P_pred) > thresholds[f] ([B] float64; -inf always and without
+        evaluating the gate, +inf or NaN never), so always-updating, gated and never-updating
+        filters share one launch, each on its own [T, B] column.  Same arguments and returns as
+        run_events otherwise."""
+        if self.model not in REF_MODELS:
+            raise ValueError('run_events_gates needs a ref15 or ref8 handle')
+        T = int(etype.shape[0])
+        et = self._dev(etype, (T, self.batch), 'etype', torch.uint8)
+        dtd = self._dev(dt, (T, self.batch), 'dt', torch.float64)
+        pay = self._dev(payload, (T, 9, self.batch), 'payload')
+        thr = self._dev(thresholds, (self.batch,), 'thresholds', torch.float64)
+        tr = self.empty(T, TRAJ_WIDTH[self.model], self.batch) if traj else None
+        ld = self.empty(T, self.batch) if logdet else None
+        up = torch.empty(T, self.batch, dtype=torch.uint8, device=self.device) if updated else None
+        cv = self.empty(T, self.ntri, self.batch) if cov else None
+        check(_lib.lib().kf_run_events_gates(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(tr), _ptr(cv),
+                                             _ptr(ld), _ptr(up), _ptr(thr), self._stream()))
+        return tr, ld, up, cv
+
     def run_stream(self, etype, dt, payload, traj=True, logdet=True, updated=False, cov=False, chunk=0,
                    warmup=-1):
         """One filter (a handle of batch 1) over a long event stream, parallel over time
@@ -491,6 +512,41 @@ class BatchedKF:
                                           self._stream()))
         combo = tuple(i for i in range(n) if (win.value >> i) & 1) if kf.value else None
         return kf.value, combo, acc, sm
+
+    def search_windows(self, events, init, prev_time, target_end, thresholds, k_max, n_events=None):
+        """Many windows' brute-force searches in one launch (kf_search_windows; the handle's
+        batch size is not used).  events: host [W, n_max, 11] float64 (t, type, payload[9]; rows
+        past n_events[w] are not read), init [W, 42], prev_time / target_end / thresholds [W],
+        n_events [W] (None: n_max everywhere).  Window w's result is search_combos(events[w,
+        :n_events[w]], init[w], prev_time[w], target_end[w], thresholds[w], min(k_max,
+        n_events[w]))'s.  Returns (k_found [W] int32, winner masks [W] uint64 (bit i = candidate
+        i), accepted counts [W, k_max + 1] uint64); mask_indices(mask) lists a winner's
+        candidates."""
+        if self.model != 'ref15':
+            raise ValueError('search_windows needs a ref15 handle')
+        ev = np.ascontiguousarray(events, dtype=np.float64)
+        if ev.ndim != 3 or ev.shape[2] != 11:
+            raise ValueError('events must be [W, n_max, 11]')
+        W, n_max = int(ev.shape[0]), int(ev.shape[1])
+        ini = np.ascontiguousarray(init, dtype=np.float64)
+        if ini.shape != (W, 42):
+            raise ValueError('init must be [W, 42]')
+
+        def per_window(a, dtype=np.float64):  # [W], a scalar standing for every window
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=dtype), (W,)))
+
+        pt, te, th = per_window(prev_time), per_window(target_end), per_window(thresholds)
+        ne = per_window(n_max if n_events is None else n_events, np.int32)
+        k_max = int(k_max)
+        win = np.zeros(W, dtype=np.uint64)
+        kf = np.zeros(W, dtype=np.int32)
+        acc = np.zeros((W, max(k_max, 0) + 1), dtype=np.uint64)
+        vp = ctypes.c_void_p
+        check(_lib.lib().kf_search_windows(self.handle, W, n_max, ne.ctypes.data_as(vp), ev.ctypes.data_as(vp),
+                                           ini.ctypes.data_as(vp), pt.ctypes.data_as(vp), te.ctypes.data_as(vp),
+                                           th.ctypes.data_as(vp), k_max, win.ctypes.data_as(vp),
+                                           kf.ctypes.data_as(vp), acc.ctypes.data_as(vp), self._stream()))
+        return kf, win, acc
 
     def search_plan(self, init, n, k_max=None, n_fixed=0, fixed_mask=0):
         """How search_combos would run over n candidates (kf_search_plan, no device work):

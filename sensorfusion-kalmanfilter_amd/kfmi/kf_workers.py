@@ -489,6 +489,33 @@ class KF_SensorFusion:
             self.indexed_sensor_data, start_idx, end_idx, R_threshold, initial_pt, initial_state,
             max_combos_in_memory=max_combos_in_memory, dtype=self.dtype, device=self.device, consts=self._consts())
 
+    def run_experiment_windows(self, start_idxs, window=25, ratios=None, thresholds=None, sweep=None,
+                               sweep_index=None, initial_pts=None, initial_states=None, k_max=4):
+        """The experiment loop's window phase (kf_workers.py:2320-2345) for every start point at
+        once (ref15.run_window_batch): windows [start_idxs[w], start_idxs[w] + window) of
+        ``indexed_sensor_data`` — full, adaptive and no-update filters and the brute-force search.
+        The warm starts are ``initial_pts`` / ``initial_states`` (P and states[-1] of each
+        window's warm-up), or come from ``sweep`` (an AdaptiveSweep, run_adaptive_threshold_sweep)
+        as sweep.warm_start(sweep_index[w], start_idxs[w]).  ``ratios``: each window's R_threshold
+        is ratios[w] times its full filter's lowest log-det, as the loop rescales its r_value
+        (:2325); ``thresholds``: R_threshold per window, as given.  Returns the WindowBatch, a
+        sequence of per-window dicts ('full', 'adaptive', 'no_update', 'brute_force',
+        'threshold') built on access."""
+        starts = [int(s) for s in start_idxs]
+        if sweep is not None:
+            if sweep_index is None:
+                raise ValueError('sweep needs sweep_index: each window\'s threshold of the sweep')
+            warm = [sweep.warm_start(int(i), s) for i, s in zip(sweep_index, starts)]
+            if any(w is None for w in warm):
+                raise ValueError('the sweep has no warm start for some window (no fix before its start)')
+            initial_states = [w[0] for w in warm]
+            initial_pts = [w[1] for w in warm]
+        if initial_pts is None or initial_states is None:
+            raise ValueError('give the warm starts: initial_pts and initial_states, or a sweep')
+        return ref15.run_window_batch(self.indexed_sensor_data, starts, [s + int(window) for s in starts], initial_pts,
+                                      initial_states, ratios=ratios, thresholds=thresholds, k_max=k_max,
+                                      dtype=self.dtype, device=self.device, consts=self._consts())
+
     def run_dead_reckoning_for_IMU(self):
         return []  # the reference's body is commented out and returns an empty list (kf_workers.py:1394-1425)
 

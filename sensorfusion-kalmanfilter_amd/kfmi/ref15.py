@@ -220,7 +220,7 @@ def event_payload(stype, sdata):
 
 
 def _run_streams(streams, x0, P0b, dtype='f64', device=0, threshold=None, model='ref15', cov=False, consts=None,
-                 kf=None):
+                 kf=None, thresholds=None):
     """Run one event list per filter in ONE kf_run_events launch.
 
     streams: list (per filter) of [(type, dt, payload9)]; each stream is preceded by a NONE
@@ -228,7 +228,8 @@ def _run_streams(streams, x0, P0b, dtype='f64', device=0, threshold=None, model=
     [B, rows] are the initial states.  Returns traj [T, W, B], logdet [T, B], updated [T, B],
     x [n, B], P blocks [rows, B], status [B] (and cov [T, rows, B] with cov=True) as NumPy
     arrays.  consts: a ModelConsts (None = the reference's constants).  kf: a handle of this
-    model, batch, dtype and constants to run on (kept open), instead of a new one."""
+    model, batch, dtype and constants to run on (kept open), instead of a new one.  thresholds
+    [B]: a gate per filter (kf_run_events_gates) instead of the one ``threshold``."""
     B = len(streams)
     T = 1 + max((len(s) for s in streams), default=0)
     etype = np.full((T, B), NONE, np.uint8)
@@ -245,7 +246,11 @@ def _run_streams(streams, x0, P0b, dtype='f64', device=0, threshold=None, model=
     npd = np.float64 if dtype == 'f64' else np.float32
     kf.set_state(np.ascontiguousarray(np.asarray(x0, np.float64).T.astype(npd)),
                  np.ascontiguousarray(np.asarray(P0b, np.float64).T.astype(npd)))
-    tr, ld, up, cv = kf.run_events(etype, dt, pay.astype(npd), updated=True, threshold=threshold, cov=cov)
+    if thresholds is not None:
+        tr, ld, up, cv = kf.run_events_gates(etype, dt, pay.astype(npd), np.asarray(thresholds, np.float64),
+                                             updated=True, cov=cov)
+    else:
+        tr, ld, up, cv = kf.run_events(etype, dt, pay.astype(npd), updated=True, threshold=threshold, cov=cov)
     x, Pb = kf.state()
     st = kf.status()
     torch.cuda.synchronize(kf.device)
@@ -264,6 +269,31 @@ def _window(events, start_idx, end_idx):
     if end_idx is None or end_idx > len(events):
         end_idx = len(events)
     return start_idx, end_idx
+
+
+def _driver_stream(window, prev, rule, predict_only=False):
+    """The (type, dt, payload) stream a list driver builds from the events ``window`` after a
+    state at time ``prev``, with its dt < 0 rule: _lib.KF_DT_FULL (run_kalman_filter_full,
+    kf_workers.py:683-685) skips the event and moves the previous time to it, KF_DT_MONOTONE
+    (the adaptive and no-update drivers, :1013-1015, :1113-1116) skips it and leaves the previous
+    time alone.  ``predict_only``: every kept event as a KF_EVENT_PREDICT with a zero payload
+    (run_no_update_kalman_filter).  Returns (stream, times of the kept events, their positions
+    in the window, previous time after the window)."""
+    stream, times, kept = [], [], []
+    for j, (_, stype, t, sdata) in enumerate(window):
+        dt = t - prev
+        if dt < 0:
+            if rule == _lib.KF_DT_FULL:
+                prev = t
+            continue
+        if predict_only:
+            stream.append((PREDICT, dt, [0.0] * 9))
+        else:
+            stream.append((GPS if stype == 'GPS' else IMU, dt, event_payload(stype, sdata)))
+        times.append(t)
+        kept.append(j)
+        prev = t
+    return stream, times, kept, prev
 
 
 def _cold_start(events, start_idx, stop):
@@ -308,15 +338,7 @@ def run_kalman_filter_full(events, start_idx=None, end_idx=None, initial_pt=None
         if cs is None:
             return [], [], []
         x0, prev, start_off = cs
-    stream, times = [], []
-    for (_, stype, t, sdata) in events[start_off:end_idx]:
-        dt = t - prev
-        if dt < 0:  # kf_workers.py:683-685
-            prev = t
-            continue
-        stream.append((GPS if stype == 'GPS' else IMU, dt, event_payload(stype, sdata)))
-        times.append(t)
-        prev = t
+    stream, times, _, prev = _driver_stream(events[start_off:end_idx], prev, _lib.KF_DT_FULL)
     tr, ld, _, x, Pb, st = _run_streams([stream], x0[None], to_blocks(P)[None], dtype, device, consts=consts)
     states = [(initial_state[0] if (initial_pt is not None and initial_state is not None) else
                events[start_off][2], *tr[0, :, 0])]
@@ -543,15 +565,8 @@ def run_adaptive_threshold_kalman_filter(events, start_idx=None, end_idx=None, R
         x0, prev, start_off = cs
         mtimes.append(prev)
     t_first = prev
-    stream, times = [], []
-    for (_, stype, t, sdata) in events[start_off:end_idx]:
-        dt = t - prev
-        if dt < 0:
-            # kf_workers.py:1013-1015 assigns an unused name, so previous_time is NOT advanced
-            continue
-        stream.append((GPS if stype == 'GPS' else IMU, dt, event_payload(stype, sdata)))
-        times.append(t)
-        prev = t
+    # kf_workers.py:1013-1015 assigns an unused name, so a skipped event does NOT advance previous_time
+    stream, times, _, prev = _driver_stream(events[start_off:end_idx], prev, _lib.KF_DT_MONOTONE)
     tr, ld, up, x, Pb, st = _run_streams([stream], x0[None], to_blocks(P)[None], dtype, device,
                                          threshold=float(R_threshold), consts=consts)
     states = [(t_first, *tr[0, :, 0])] + [(t, *tr[i + 1, :, 0]) for i, t in enumerate(times)]
@@ -789,14 +804,7 @@ def run_no_update_kalman_filter(events, start_idx=None, end_idx=None, R_threshol
         x0, prev, start_off = cs
         mtimes.append(prev)
     t_first = prev
-    stream, times = [], []
-    for (_, stype, t, sdata) in events[start_off:end_idx]:
-        dt = t - prev
-        if dt < 0:
-            continue
-        stream.append((PREDICT, dt, [0.0] * 9))
-        times.append(t)
-        prev = t
+    stream, times, _, prev = _driver_stream(events[start_off:end_idx], prev, _lib.KF_DT_MONOTONE, predict_only=True)
     tr, ld, _, _, Pb, _ = _run_streams([stream], x0[None], to_blocks(P)[None], dtype, device, consts=consts)
     states = [(t_first, *tr[0, :, 0])] + [(t, *tr[i + 1, :, 0]) for i, t in enumerate(times)]
     logdets = [float(v) for v in ld[:len(times) + 1, 0]]
@@ -1267,6 +1275,259 @@ def run_brute_force_kalman_filter_no_sampling_min_usage(events, start_idx=0, end
                                   consts=consts, kf=kf)
     finally:
         kf.close()
+
+
+# --------------------------------------------------------------------------------------------
+# The experiment loop's windows as one batch (kf_workers.py:2320-2345)
+# --------------------------------------------------------------------------------------------
+
+def _window_rule(tt, ee, pp, valid, prev_times, rule):
+    """window_arrays on gathered entries: tt / ee [L, B] and pp [L, B, 9] are the stream's times,
+    types and payloads at the windows' entries, valid [L, B] marks the entries inside each
+    window (a prefix of every column)."""
+    prev0 = np.asarray(prev_times, np.float64)[None, :]
+    before = np.concatenate([prev0, tt[:-1]], axis=0)  # the previous entry's time (prev_time for the first)
+    if rule == _lib.KF_DT_MONOTONE:
+        before = np.maximum.accumulate(before, axis=0)  # skipped events do not move the previous time
+    elif rule != _lib.KF_DT_FULL:
+        raise ValueError('rule must be KF_DT_FULL or KF_DT_MONOTONE')
+    d = tt - before
+    et = np.where(valid, np.where(d < 0, NONE, ee), NONE).astype(np.uint8)
+    dt = np.where(valid, d, 0.0)
+    pay = np.where(valid[:, :, None], pp, 0.0)
+    return et, dt, np.ascontiguousarray(pay.transpose(0, 2, 1))
+
+
+def _window_index(start_idxs, lengths):
+    """(entry indices [L, B] clipped into their windows, valid [L, B]) of B windows, L the longest."""
+    starts = np.asarray(start_idxs, np.int64).reshape(-1)
+    lens = np.asarray(lengths, np.int64).reshape(-1)
+    L = int(lens.max()) if lens.size else 0
+    j = np.arange(L, dtype=np.int64)[:, None]
+    valid = j < lens[None, :]
+    return np.where(valid, starts[None, :] + j, starts[None, :]), valid
+
+
+def window_arrays(t, etype, payload, start_idxs, lengths, prev_times, rule):
+    """The [L][B] event arrays of B windows of one merged stream, one window per filter, as the
+    per-window drivers build them: window w holds entries start_idxs[w] .. start_idxs[w] +
+    lengths[w] - 1 of the stream (t [N] float64, etype [N] uint8, payload [N, 9]; host arrays)
+    after a state at time prev_times[w], and L = max(lengths).  ``rule`` is kf_events_dt's:
+    _lib.KF_DT_FULL (run_kalman_filter_full: dt against the previous entry's time, skipped or
+    not) or _lib.KF_DT_MONOTONE (the adaptive and no-update drivers: against the latest time so
+    far); an entry with dt < 0 becomes KF_EVENT_NONE and keeps its dt and payload, as
+    kf_events_dt leaves them.  Entries past a window's length are KF_EVENT_NONE with zero dt and
+    payload.  Returns (etype [L, B] uint8, dt [L, B] float64, payload [L, 9, B] float64)."""
+    t = np.asarray(t, np.float64)
+    idx, valid = _window_index(start_idxs, lengths)
+    if valid.any() and (idx.min() < 0 or idx.max() >= len(t)):
+        raise ValueError('a window reaches outside the stream')
+    return _window_rule(t[idx], np.asarray(etype)[idx], np.asarray(payload, np.float64)[idx], valid, prev_times, rule)
+
+
+class WindowBatch:
+    """run_window_batch's results: a sequence over the windows whose entry w is built on access,
+    a dict of what the experiment loop takes from its four calls on that window
+    (kf_workers.py:2320-2345), in the single drivers' layouts:
+      'full'        run_kalman_filter_full's (states, logdets, P, prev_time)
+      'adaptive'    run_adaptive_threshold_kalman_filter's (states, logdets, P, previous_time,
+                    measurement_times) at 'threshold'
+      'no_update'   run_no_update_kalman_filter's 5-tuple
+      'brute_force' run_brute_force_kalman_filter_no_sampling_min_usage's result dict or None
+      'threshold'   the window's R_threshold (its ratio times the full filter's lowest log-det)
+    ``k_found`` [W], ``winners`` (index tuples or None) and ``thresholds`` [W] are NumPy / lists
+    for the whole batch; ``fallback`` lists the windows that went through the one-window search."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return len(self.thresholds)
+
+    def _filter(self, col, t_all, keep, rule_prev):
+        states = [(float(t_all[i]), *self._traj[i, :, col].tolist()) for i in np.nonzero(keep)[0]]
+        return states, self._ld[keep, col].tolist(), from_blocks(self._Pb[:, col]), rule_prev
+
+    def __getitem__(self, w):
+        W = len(self)
+        if isinstance(w, slice):
+            return [self[i] for i in range(*w.indices(W))]
+        if w < 0:
+            w += W
+        if not 0 <= w < W:
+            raise IndexError(w)
+        L = int(self._lens[w])
+        prev0 = float(self._prev0[w])
+        t_all = np.concatenate([[prev0], self._tt[:L, w]])
+        # masks over all L_max + 1 record rows: the entries past this window's length are NONE
+        kfull, km = self._keep_full[:, w].copy(), self._keep_mono[:, w].copy()
+        kfull[0] = km[0] = True  # the leading NONE entry records the initial state
+        full = self._filter(w, t_all, kfull, float(t_all[-1]) if L else prev0)
+        tk = t_all[km[:L + 1]]
+        prev_m = float(tk[-1]) if len(tk) > 1 else prev0
+        upd = (self._up[:, W + w].astype(bool) & km)[:L + 1]
+        upd[0] = False
+        adaptive = self._filter(W + w, t_all, km, prev_m) + (t_all[upd].tolist(),)
+        no_update = self._filter(2 * W + w, t_all, km, prev_m) + ([],)
+        return {'full': full, 'adaptive': adaptive, 'no_update': no_update, 'brute_force': self._brute(w),
+                'threshold': float(self.thresholds[w])}
+
+    def _brute(self, w):
+        if w in self._fallback_results:
+            return self._fallback_results[w]
+        idx = self.winners[w]
+        if idx is None:
+            return None
+        f = self._win_col[w]
+        if self._win_status[f] != 0:
+            return None
+        s = int(self._starts[w])
+        combo = tuple(self._events[s + i] for i in idx)
+        times = self._win_times[f]
+        traj = [(float(self._prev0[w]), *self._win_traj[0, :, f].tolist())]
+        traj += [(t, *self._win_traj[i + 1, :, f].tolist()) for i, t in enumerate(times)]
+        return {'selected_sensors': combo, 'final_state': self._win_x[:, f].copy(), 'final_covariance': None,
+                'trajectory': traj, 'accuracy_metric': 0,
+                'log_determinants': [float(v) for v in self._win_ld[:len(times) + 1, f]],
+                'num_measurements_used': len(combo)}
+
+
+def run_window_batch(events, start_idxs, end_idxs, initial_pts, initial_states, ratios=None, thresholds=None, k_max=4,
+                     dtype='f64', device=0, consts=None):
+    """The experiment loop's window phase (kf_workers.py:2320-2345) for W windows at once: each
+    window [start_idxs[w], end_idxs[w]) of ``events`` (an ingested stream, an event list over one,
+    or a plain event list) from its warm start initial_pts[w] (15x15) / initial_states[w]
+    (states[-1] of the warm-up: x[0:6] = state[1:7], the other nine states zero, previous time =
+    state[0]; :643-646, :978-981).  In order:
+      1. the W full filters (run_kalman_filter_full) in one kf_run_events_gates launch;
+      2. each window's threshold: ratios[w] times its full filter's lowest log-det (:2325), or
+         thresholds[w] as given;
+      3. the W adaptive and W no-update filters in one launch on a handle of 2 W filters (gates
+         thresholds[w], and -inf over KF_EVENT_PREDICT events);
+      4. every window's search over the sizes 1 .. k_max in one kf_search_windows call;
+      5. the winners' own filters (the subset's events, then the predict to the window's end) as
+         one more ragged batch, for the result dict's log_determinants, final_state, trajectory;
+      6. a window without an accepted subset up to k_max goes through
+         run_brute_force_kalman_filter_no_sampling_min_usage, one window per call as before.
+    Returns a WindowBatch."""
+    if (ratios is None) == (thresholds is None):
+        raise ValueError('give either ratios or thresholds')
+    starts = np.asarray(start_idxs, np.int64).reshape(-1)
+    ends = np.asarray(end_idxs, np.int64).reshape(-1)
+    W = len(starts)
+    ds = _device_stream(events)
+    n_all = len(ds) if ds is not None else len(events)
+    ends = np.minimum(ends, n_all)
+    lens = ends - starts
+    if W == 0 or len(ends) != W or len(initial_pts) != W or len(initial_states) != W:
+        raise ValueError('start_idxs, end_idxs, initial_pts and initial_states must list the same W >= 1 windows')
+    if lens.min() < 1 or starts.min() < 0:
+        raise ValueError('every window needs at least one event inside the stream')
+    if lens.max() > 64:
+        raise ValueError(f'{int(lens.max())} candidate events: the GPU search supports at most 64')
+    idx, valid = _window_index(starts, lens)
+    L = idx.shape[0]
+    if ds is not None:  # the stream's host copy (cached by the stream): the windows' entries by index
+        h = ds.host()
+        tt, ee, pp = h['t'][idx].astype(np.float64), h['etype'][idx], h['payload'][idx].astype(np.float64)
+        device = ds.t.device.index or 0
+    else:
+        tt, ee, pp = np.zeros((L, W)), np.zeros((L, W), np.uint8), np.zeros((L, W, 9))
+        for w in range(W):
+            for j, (_, stype, t, sdata) in enumerate(events[int(starts[w]):int(ends[w])]):
+                tt[j, w], ee[j, w], pp[j, w] = t, GPS if stype == 'GPS' else IMU, event_payload(stype, sdata)
+    x0 = np.zeros((W, 15))
+    x0[:, 0:6] = np.asarray([s[1:7] for s in initial_states], np.float64)
+    prev0 = np.asarray([s[0] for s in initial_states], np.float64)
+    P0b = np.stack([to_blocks(np.asarray(P, np.float64)) for P in initial_pts])
+    et_f, dt_f, pay_f = _window_rule(tt, ee, pp, valid, prev0, _lib.KF_DT_FULL)
+    et_m, dt_m, pay_m = _window_rule(tt, ee, pp, valid, prev0, _lib.KF_DT_MONOTONE)
+
+    def lead(et, dt, pay):  # a NONE event first records the initial state and logdet
+        return (np.concatenate([np.full((1,) + et.shape[1:], NONE, np.uint8), et]),
+                np.concatenate([np.zeros((1,) + dt.shape[1:]), dt]),
+                np.concatenate([np.zeros((1,) + pay.shape[1:]), pay]))
+    # the records' columns: [0, W) full, [W, 2W) adaptive, [2W, 3W) no-update.  The full filters
+    # run first, on a handle of W filters (the thresholds come from their log-dets); the adaptive
+    # and no-update filters then share one launch on a handle of 2 W
+    et_p = np.where(et_m != NONE, PREDICT, NONE).astype(np.uint8)
+    et1, dt1, pay1 = lead(et_f, dt_f, pay_f)
+    et2, dt2, pay2 = lead(np.concatenate([et_m, et_p], 1), np.concatenate([dt_m, dt_m], 1),
+                          np.concatenate([pay_m, np.zeros_like(pay_m)], 2))
+    npd = np.float64 if dtype == 'f64' else np.float32
+    inf = float('inf')
+    kf1 = BatchedKF('ref15', W, dtype, device=device, params=_params(consts))
+    kf = BatchedKF('ref15', 2 * W, dtype, device=device, params=_params(consts))
+    try:
+        xs, Ps = np.ascontiguousarray(x0.T.astype(npd)), np.ascontiguousarray(P0b.T.astype(npd))
+        kf1.set_state(xs, Ps)
+        tr1, ld1, up1, _ = kf1.run_events_gates(et1, dt1, pay1.astype(npd), np.full(W, -inf), updated=True)
+        keep_full = et1 != NONE
+        if thresholds is None:
+            rec = keep_full.copy()
+            rec[0] = True  # logdets[0], the initial covariance's, is in the driver's list too
+            low = np.where(rec, ld1.double().cpu().numpy(), np.inf).min(axis=0)
+            thr = np.asarray(ratios, np.float64).reshape(-1) * low
+        else:
+            thr = np.asarray(thresholds, np.float64).reshape(-1).copy()
+        if thr.shape != (W,):
+            raise ValueError('ratios / thresholds must hold one value per window')
+        kf.set_state(np.tile(xs, (1, 2)), np.tile(Ps, (1, 2)))
+        tr2, ld2, up2, _ = kf.run_events_gates(et2, dt2, pay2.astype(npd), np.concatenate([thr, np.full(W, -inf)]),
+                                               updated=True)
+        st = torch.cat([kf1.status(), kf.status()])
+        traj = torch.cat([tr1, tr2], 2).double().cpu().numpy()
+        ld = torch.cat([ld1, ld2], 1).double().cpu().numpy()
+        up = torch.cat([up1, up2], 1).cpu().numpy()
+        Pb_h = torch.cat([kf1.state()[1], kf.state()[1]], 1).double().cpu().numpy()
+        # 4. the searches
+        ev = np.zeros((W, L, 11))
+        ev[:, :, 0] = tt.T
+        ev[:, :, 1] = ee.T
+        ev[:, :, 2:] = pp.transpose(1, 0, 2)
+        init = np.concatenate([x0, P0b], 1)
+        target_end = tt[lens - 1, np.arange(W)]
+        k_found, masks, acc = kf.search_windows(ev, init, prev0, target_end, thr, int(k_max), n_events=lens)
+    finally:
+        kf1.close()
+        kf.close()
+    winners = [tuple(i for i in range(int(lens[w])) if (int(masks[w]) >> i) & 1) if k_found[w] else None
+               for w in range(W)]
+    # 5. the winners' own filters, one ragged batch (the combination worker's rules, kf_workers.py:36-82)
+    cols, streams, times_l = {}, [], []
+    for w in range(W):
+        if winners[w] is None:
+            continue
+        s, times, cur = [], [], prev0[w]
+        for i in winners[w]:
+            d = tt[i, w] - cur
+            if d < 0:
+                continue
+            s.append((int(ee[i, w]), d, pp[i, w]))
+            times.append(float(tt[i, w]))
+            cur = tt[i, w]
+        if cur < target_end[w] - 1e-8:
+            s.append((PREDICT, target_end[w] - cur, np.zeros(9)))
+            times.append(float(target_end[w]))
+        cols[w] = len(streams)
+        streams.append(s)
+        times_l.append(times)
+    win = dict(_win_col=cols, _win_times=times_l, _win_traj=None, _win_ld=None, _win_x=None, _win_status=None)
+    if streams:
+        sel = np.asarray(list(cols))
+        wtr, wld, _, wx, _, wst = _run_streams(streams, x0[sel], P0b[sel], dtype, device, consts=consts,
+                                               thresholds=np.full(len(streams), -inf))
+        win.update(_win_traj=wtr, _win_ld=wld, _win_x=wx, _win_status=wst)
+    # 6. windows without an accepted subset up to k_max: the one-window search, as before
+    fallback = {}
+    for w in np.nonzero(np.asarray(k_found) == 0)[0]:
+        fallback[int(w)] = run_brute_force_kalman_filter_no_sampling_min_usage(
+            events, int(starts[w]), int(ends[w]), float(thr[w]), initial_pts[w], initial_states[w], dtype=dtype,
+            device=device, consts=consts)
+    return WindowBatch(thresholds=thr, k_found=np.asarray(k_found), winners=winners, n_accepted=acc,
+                       fallback=sorted(fallback), status=st.cpu().numpy(), _fallback_results=fallback, _events=events,
+                       _starts=starts, _lens=lens, _prev0=prev0, _tt=tt, _traj=traj, _ld=ld, _up=up, _Pb=Pb_h,
+                       _keep_full=keep_full, _keep_mono=et2[:, :W] != NONE, **win)
 
 
 # --------------------------------------------------------------------------------------------
