@@ -31,13 +31,13 @@
  * All functions return KF_OK (0) or a negative KF_E* code; kf_last_error() then
  * describes the failure (thread-local).  Launching entry points are asynchronous on
  * the given hipStream_t (NULL = the null stream) and never synchronise, so they can be
- * captured into a hipGraph.  Workspaces: kf_search_combos, kf_search_windows, kf_run_stream and
- * kf_run_scheduled(_rec) keep a device workspace in the handle, allocated by the first call
- * that needs it and grown (hipMalloc; hipFree synchronises the device) only by a call that
+ * captured into a hipGraph.  Workspaces: kf_search_combos, kf_search_windows, kf_run_stream,
+ * kf_run_tails and kf_run_scheduled(_rec) keep a device workspace in the handle, allocated by
+ * the first call that needs it and grown (hipMalloc; hipFree synchronises the device) only by a call that
  * needs more than every earlier one; every other launch allocates nothing.  Run such a call
  * once eagerly before capturing it: inside a capture nothing is allocated (kf_run_scheduled
- * then takes its fused kernel, kf_run_stream returns KF_EINVAL; kf_search_combos and
- * kf_search_windows synchronise and are never captured).  A workspace a capture used
+ * then takes its fused kernel, kf_run_stream and kf_run_tails return KF_EINVAL; kf_search_combos
+ * and kf_search_windows synchronise and are never captured).  A workspace a capture used
  * is never freed before kf_free, so a graph stays valid after a later, larger eager call: each
  * such growth keeps the smaller buffer (retired) until kf_free or kf_release_retired, so a
  * handle that alternates captures with ever-larger eager calls holds all of them.
@@ -409,6 +409,36 @@ int kf_run_stream(kf_batch* handle, int T, const uint8_t* etype, const double* d
 int kf_run_sweep(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
                  const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
                  int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
+
+/* Ragged tails of ONE event stream in one launch: the handle's B filters are B independent gated
+ * runs over different ranges of the same stream from different start states.  KF_MODEL_REF15 /
+ * KF_MODEL_REF8.  etype / dt / payload: kf_run_sweep's device [T], [T], [T][9].  Tail f runs the
+ * events [lo[f], hi[f]) with kf_run_sweep's event step against thresholds[f] (device [B] double,
+ * the same conventions).  Its start state is row src_row[f], column src_col[f] of src_x device
+ * [src_rows][n][src_batch] and src_P device [src_rows][27][src_batch] (REF8: 15 rows), the
+ * layout of kf_run_sweep's ckpt_x / ckpt_P, so a sweep's checkpoints are passed as they are, with
+ * status KF_OK as after kf_set_state; src_row[f] = -1 starts from the handle's own column f and
+ * its status.  The end state and status (KF_ENOTSPD for a tail that failed, that tail only) go
+ * to the handle's column f, the tail's applied updates to n_updated device [B] int32 (NULL =
+ * skip).  No per-event records and no checkpoints: kf_run_events_gates records a tail.  A tail
+ * of length 0 copies its source state to the handle bit for bit; T = 0 with every lo = hi = 0
+ * is legal.  lo, hi, src_row, src_col are HOST [B] arrays, checked before anything is queued
+ * (KF_EINVAL naming the tail, never clamped or wrapped): 0 <= lo <= hi <= T, -1 <= src_row <
+ * src_rows, 0 <= src_col < src_batch where src_row >= 0, src_x / src_P non-NULL if any src_row
+ * >= 0.  They reach the device through a handle workspace ("Workspaces" above: grown on demand,
+ * KF_EINVAL inside a capture that would have to grow it), and the caller may reuse them when the
+ * call returns.  Limits (KF_EINVAL): 9 T w < 4 GiB, 27 B w < 2 GiB, and one source row span
+ * 27 src_batch w < 2 GiB; the source rows are addressed from 64-bit bases, so src_rows has no
+ * limit.  One wave carries 8 tails and runs to its longest, the finished ones predicated off:
+ * a call costs the sum over waves of the longest tail in each, so sort the tails by length.
+ * Asynchronous on `stream`.  Replaces the warm-up run_adaptive_threshold_kalman_filter call
+ * from event 0 to start_idx that the experiment loop makes per iteration
+ * (kf_workers.py:2306-2317): every iteration's tail past its checkpoint in one launch. */
+int kf_run_tails(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                 const int32_t* lo, const int32_t* hi, const double* thresholds,
+                 const void* src_x, const void* src_P, int src_rows, int64_t src_batch,
+                 const int32_t* src_row, const int32_t* src_col,
+                 int32_t* n_updated, void* stream);
 
 /* The checks of the handle's last kf_run_stream (synchronises `stream`): out[0] = 1 if the
  * chunked run's records stood (0: the sequential fallback ran), out[1] = 1 if a chunk filter

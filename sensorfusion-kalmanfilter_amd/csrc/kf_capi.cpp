@@ -83,6 +83,11 @@ struct kf_batch {
     uint64_t* win_host;
     uint64_t* win_host_dev;
     size_t win_host_words;
+    // kf_run_tails: the tails' (lo, hi, src_row, src_col) on the device, [B] TailSpec (grown on demand)
+    void* tails_ws;
+    size_t tails_ws_bytes;
+    bool tails_ws_graph;
+    std::vector<kfmi::TailSpec> tails_host;  // the table's host image: it outlives the call that uploads it
 };
 
 namespace {
@@ -626,6 +631,7 @@ int kf_free(kf_batch* h) {
     if (h->pend_done) (void)hipEventDestroy(h->pend_done);
     if (h->kc) (void)hipFree(h->kc);
     if (h->sched_ws) (void)hipFree(h->sched_ws);
+    if (h->tails_ws) (void)hipFree(h->tails_ws);
     for (auto& r : h->retired) (void)hipFree(r.first);
     delete h;
     return KF_OK;
@@ -1021,6 +1027,79 @@ int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, con
     hipError_t e = kfmi::launch_ref_sweep(h->model == KF_MODEL_REF15 ? 15 : 8, h->dtype == KF_F64, a,
                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? KF_OK : hip_fail(e, "kf_run_sweep");
+}
+
+int kf_run_tails(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, const int32_t* lo,
+                 const int32_t* hi, const double* thresholds, const void* src_x, const void* src_P, int src_rows,
+                 int64_t src_batch, const int32_t* src_row, const int32_t* src_col, int32_t* n_updated, void* stream) {
+    if (int rc = check_handle(h)) return rc;
+    if (!is_ref(h)) return fail(KF_EINVAL, "kf_run_tails: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle");
+    if (T < 0) return fail(KF_EINVAL, "kf_run_tails: T = %d < 0", T);
+    if (src_rows < 0 || src_batch < 0)
+        return fail(KF_EINVAL, "kf_run_tails: src_rows = %d, src_batch = %lld: negative", src_rows, (long long)src_batch);
+    if (h->B == 0) return KF_OK;
+    if (!lo || !hi || !src_row || !src_col) return fail(KF_EINVAL, "kf_run_tails: null lo/hi/src_row/src_col array");
+    if (T > 0 && (!etype || !dt || !payload)) return fail(KF_EINVAL, "kf_run_tails: null etype/dt/payload stream");
+    if (!thresholds) return fail(KF_EINVAL, "kf_run_tails: null thresholds");
+    // the kernel's descriptors: the stream by byte range (32-bit), the handle's state rows as one
+    // span whose offsets keep bit 31 free; a source row is addressed from a 64-bit base
+    const uint64_t w = elem(h);
+    if (uint64_t(T) * 9u * w >= (uint64_t(1) << 32))
+        return fail(KF_EINVAL, "kf_run_tails: T = %d events exceed the 4 GiB payload descriptor (9 T w)", T);
+    if (uint64_t(h->B) * 27u * w >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "kf_run_tails: B = %lld tails exceed the 2 GiB state span (27 B w)", (long long)h->B);
+    if (uint64_t(src_batch) * 27u * w >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "kf_run_tails: src_batch = %lld columns exceed the 2 GiB source row span (27 src_batch w)",
+                    (long long)src_batch);
+    // every tail is checked before anything is queued: nothing is clamped or wrapped
+    std::vector<kfmi::TailSpec>& spec = h->tails_host;
+    spec.resize(static_cast<size_t>(h->B));
+    for (int64_t f = 0; f < h->B; ++f) {
+        if (lo[f] < 0 || lo[f] > hi[f] || hi[f] > T)
+            return fail(KF_EINVAL, "kf_run_tails: tail %lld: events [%d, %d) are not 0 <= lo <= hi <= T = %d",
+                        (long long)f, lo[f], hi[f], T);
+        if (src_row[f] < -1 || src_row[f] >= src_rows)
+            return fail(KF_EINVAL, "kf_run_tails: tail %lld: src_row = %d is not in [-1, src_rows = %d)", (long long)f,
+                        src_row[f], src_rows);
+        if (src_row[f] >= 0) {
+            if (src_col[f] < 0 || src_col[f] >= src_batch)
+                return fail(KF_EINVAL, "kf_run_tails: tail %lld: src_col = %d is not in [0, src_batch = %lld)",
+                            (long long)f, src_col[f], (long long)src_batch);
+            if (!src_x || !src_P)
+                return fail(KF_EINVAL, "kf_run_tails: tail %lld: src_row = %d with null src_x/src_P", (long long)f,
+                            src_row[f]);
+        }
+        spec[size_t(f)] = kfmi::TailSpec{lo[f], hi[f], src_row[f], src_row[f] >= 0 ? src_col[f] : 0};
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t need = sizeof(kfmi::TailSpec) * spec.size();
+    if (!grow_ws(h, &h->tails_ws, &h->tails_ws_bytes, &h->tails_ws_graph, need, st))
+        return capturing(st) ? fail(KF_EINVAL, "kf_run_tails: the tail table (%zu bytes) must be sized by an eager call "
+                                               "before a graph capture", need)
+                             : fail(KF_EHIP, "kf_run_tails: cannot allocate %zu bytes for the tail table", need);
+    if (capturing(st)) h->tails_ws_graph = true;
+    // from pageable memory: the copy has read the caller's arrays (packed into the handle's image)
+    // when the call returns
+    hipError_t e = hipMemcpyAsync(h->tails_ws, spec.data(), need, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e, "kf_run_tails: tail table upload");
+    kfmi::SweepArgs a{};
+    a.B = h->B;
+    a.T = T;
+    a.etype = etype;
+    a.dt = dt;
+    a.payload = payload;
+    a.thresholds = thresholds;
+    a.x = h->x;
+    a.P = h->P;
+    a.status = h->status;
+    a.n_updated = n_updated;
+    a.kc = h->kc;
+    a.tails = static_cast<const kfmi::TailSpec*>(h->tails_ws);
+    a.src_x = src_x;
+    a.src_P = src_P;
+    a.src_B = src_batch;
+    e = kfmi::launch_ref_tails(h->model == KF_MODEL_REF15 ? 15 : 8, h->dtype == KF_F64, a, st);
+    return e == hipSuccess ? KF_OK : hip_fail(e, "kf_run_tails");
 }
 
 int kf_run_stream(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, void* traj,

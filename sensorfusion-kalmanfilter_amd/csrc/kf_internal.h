@@ -104,6 +104,13 @@ struct RefArgs {
     StreamCheck* s_check;
 };
 
+// One tail of kf_run_tails: its event range of the shared stream and where its start state lies
+struct TailSpec {
+    int32_t lo, hi;          // events [lo, hi), 0 <= lo <= hi <= T (checked on the host)
+    int32_t src_row;         // row of src_x / src_P, or -1: the handle's own column
+    int32_t src_col;         // column of that row (unused with src_row = -1)
+};
+
 // Threshold sweep (kf_run_sweep, kf_workers.py:959-1058 under the thresholds of :2298-2317): the
 // handle's B filters all run the ONE stream etype / dt / payload ([T], [T], [T][9]) from their own
 // start states, filter f gated by thresholds[f].
@@ -125,6 +132,14 @@ struct SweepArgs {
     void* ckpt_x;            // [T / ckpt_every][N][B]
     void* ckpt_P;            // [T / ckpt_every][NBLK][B]
     const RefConsts* kc;     // the handle's own noise constants (device), or nullptr: the reference's
+    // Tails mode (kf_run_tails; the TAILS instantiations only): filter f runs the events
+    // [tails[f].lo, tails[f].hi) of the stream from row src_row, column src_col of src_x / src_P
+    // (ckpt_x / ckpt_P's layout with src_B columns; src_row = -1: the handle's own column f), and
+    // writes no records and no checkpoints
+    const TailSpec* tails;   // device [B]
+    const void* src_x;       // [R][N][src_B]
+    const void* src_P;       // [R][NBLK][src_B]
+    int64_t src_B;
 };
 
 // Time-parallel run of one filter over a long event stream (kf_run_stream): the state banks of
@@ -410,6 +425,8 @@ hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t 
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv = 1);
 // one stream under the handle's B thresholds (ref_sweep_kernel: 8 lanes per filter)
 hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream);
+// ragged tails of one stream (ref_sweep_kernel's TAILS instantiations; a.tails set, a.T >= 0)
+hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream);
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream);
 hipError_t launch_ref15_combos(bool f64, const Ref15ComboArgs& a, hipStream_t stream);
 // child_major: one wave per (parent block, child event) instead of one lane per parent

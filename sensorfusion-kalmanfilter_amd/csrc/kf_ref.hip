@@ -1189,6 +1189,15 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 // pays the update whenever one of its groups applies it: a sweep costs about what its
 // most-updating threshold costs.  Records in kf_run_events' layouts ([T][W][B], [T][B]), an
 // update count per filter, and the handle-layout state every ckpt_every events.
+//
+// TAILS (kf_run_tails): the same groups as ragged tails of the one stream.  Group f gathers its
+// start state itself (row tails[f].src_row, column src_col of src_x / src_P, or its own handle
+// column), runs the events [lo, hi) of the stream and writes its end state to handle column f; no
+// records, no checkpoints.  The event's type and dt are the group's own, so the NONE / GPS / IMU
+// branches diverge between groups (a group is active or inactive as a whole: its DPP reductions
+// stay legal).  The wave runs to its longest tail with the finished groups predicated off, and
+// the input ring clamps per group to the tail's own last event; an empty tail loads nothing.
+// Every other instantiation compiles to the code it was.
 // ------------------------------------------------------------------------------------
 #ifndef KF_SWEEP_DEPTH
 #define KF_SWEEP_DEPTH 4
@@ -1196,10 +1205,24 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 constexpr int kSweepDepth = KF_SWEEP_DEPTH;  // input ring of ref_sweep_kernel
 constexpr int kSweepBlock = 64;              // one wave (8 thresholds) per workgroup: waves spread over the CUs
 
-template <typename T, class M, bool CUSTOM>
+template <typename T, class M, bool CUSTOM, bool TAILS = false>
 __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs a) {
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
     const int64_t f = g / kGroup;
+    // TAILS: the group's tail, and the wave's longest (every lane of the wave takes part in the
+    // reduction, the groups past B with length 0, before those leave)
+    TailSpec tl{0, 0, -1, 0};
+    int len = 0, wave_len = 0;
+    if constexpr (TAILS) {
+        if (f < a.B) {
+            tl = a.tails[f];
+            len = tl.hi - tl.lo;
+        }
+        wave_len = len;
+#pragma unroll
+        for (int sh = kGroup; sh < 64; sh <<= 1) wave_len = max(wave_len, __shfl_xor(wave_len, sh, 64));
+        wave_len = wave_uniform(wave_len);
+    }
     if (f >= a.B) return;  // whole groups leave together
     const int c = static_cast<int>(g % kGroup);
     const bool pva = c < M::NP;
@@ -1240,14 +1263,28 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     }
 
     T x[1][3], P[6];
-    {
+    if constexpr (TAILS) {
+        // the group's own source column (64-bit addressing: row src_row of [R][rows][src_B]), or
+        // its handle column; the rows a lane does not hold keep the handle load's 0 / 1
+        const bool own = tl.src_row < 0;
+        const int64_t sb = own ? a.B : a.src_B;
+        const T* sx = own ? static_cast<const T*>(a.x) + f
+                          : static_cast<const T*>(a.src_x) + int64_t(tl.src_row) * M::N * sb + tl.src_col;
+        const T* sp = own ? static_cast<const T*>(a.P) + f
+                          : static_cast<const T*>(a.src_P) + int64_t(tl.src_row) * M::NBLK * sb + tl.src_col;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[0][k] = xi[k] >= 0 ? sx[int64_t(xi[k]) * sb] : T(0);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? sp[int64_t(pr[k]) * sb] : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+    } else {
         const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[0][k] = ldv(rx, vx[k], T(0));
 #pragma unroll
         for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
     }
-    int32_t st = a.status[f];
+    // a tail from a source column starts with status OK, as after kf_set_state
+    int32_t st = (TAILS && tl.src_row >= 0) ? 0 : a.status[f];
     int32_t nup = 0;
     // the group's threshold; NaN never opens the gate (every comparison with it is false), and
     // -inf is "always update": the gate is not evaluated (a covariance that is not positive
@@ -1257,7 +1294,8 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     const bool always = thr_d == -__builtin_inf();
     GateBand<T> gate;
     gate.init(thr_d);
-    const bool need_tr = a.traj != nullptr, need_ld = a.logdet != nullptr, need_up = a.updated != nullptr;
+    const bool need_tr = !TAILS && a.traj != nullptr, need_ld = !TAILS && a.logdet != nullptr;
+    const bool need_up = !TAILS && a.updated != nullptr;
 
     const uint32_t S = uint32_t(a.T);
     const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
@@ -1269,11 +1307,11 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
         in.va = ldv(r_pay, (ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T)), T(0));
         in.vb = ldv(r_pay, (ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T)), T(0));
     };
-    int ck_left = a.ckpt_every;  // events until the next checkpoint (wave-uniform)
+    int ck_left = TAILS ? 0 : a.ckpt_every;  // events until the next checkpoint (wave-uniform)
     int ck_row = 0;
     auto step = [&](int t, const ChainIn<T>& in) {
-        // every lane of the wave loaded the same type and dt: scalars
-        const int type = wave_uniform(in.type);
+        // every lane of the wave loaded the same type and dt: scalars (TAILS: the group's own)
+        const int type = TAILS ? in.type : wave_uniform(in.type);
         const T dt = T(in.dt);
         const T va = in.va, vb = in.vb;
         bool applied = false;
@@ -1362,7 +1400,42 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     // the chain kernel's input ring (kSweepDepth - 1 events ahead; loads past the end re-read
     // the last event)
     constexpr int D = kSweepDepth;
-    const int T_ = a.T;
+    if constexpr (TAILS) {
+        // the same ring over the wave's longest tail: step s is the group's event lo + s, loaded
+        // through the stream's descriptors at that offset and clamped to the tail's own last event
+        // (so never past T - 1); a group past its tail is predicated off, and an empty tail's
+        // loads are dropped (offset 2^32 - 1 lies past every byte range, the 4 GiB payload's too)
+        const uint32_t dead = len > 0 ? 0u : ~0u;
+        auto load_t = [&](int s, ChainIn<T>& in) {
+            const uint32_t ue = uint32_t(tl.lo + (s < len ? s : len - 1));
+            in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue | dead, 0, 0));
+            in.dt = ldv(r_dt, (ue * 8u) | dead, 0.0);
+            in.va = ldv(r_pay, ((ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T))) | dead, T(0));
+            in.vb = ldv(r_pay, ((ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T))) | dead, T(0));
+        };
+        auto step_t = [&](int s, const ChainIn<T>& in) {
+            if (s < len) step(s, in);
+        };
+        const int W_ = wave_len;  // finite, wave-uniform, known before the loop
+        if (W_ > 0) {
+            ChainIn<T> buf[D];
+#pragma unroll
+            for (int j = 0; j < D - 1; ++j) load_t(j, buf[j]);
+            __builtin_amdgcn_s_waitcnt(0);
+            int s = 0;
+            for (; s + D <= W_; s += D) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    load_t(s + j + D - 1, buf[(j + D - 1) % D]);
+                    step_t(s + j, buf[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < D - 1; ++j)
+                if (s + j < W_) step_t(s + j, buf[j]);
+        }
+    }
+    const int T_ = TAILS ? 0 : a.T;
     auto load_c = [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); };
     if (T_ > 0) {
         ChainIn<T> buf[D];
@@ -4737,6 +4810,21 @@ hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t 
         } else {
             if (f64) ref_stream_t<double, M8, CUSTOM>(a, stream, nv);
             else ref_stream_t<float, M8, CUSTOM>(a, stream, nv);
+        }
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
+    if (a.B <= 0 || a.T < 0 || !a.tails || (model != 15 && model != 8)) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
+    KF_CUSTOM_DISPATCH(a.kc, {
+        if (model == 15) {
+            if (f64) ref_sweep_kernel<double, M15, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
+            else ref_sweep_kernel<float, M15, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
+        } else {
+            if (f64) ref_sweep_kernel<double, M8, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
+            else ref_sweep_kernel<float, M8, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
         }
     });
     return hipGetLastError();

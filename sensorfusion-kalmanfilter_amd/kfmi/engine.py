@@ -444,6 +444,50 @@ class BatchedKF:
                                       self._stream()))
         return tr, ld, up, nu, cx, cP
 
+    def run_tails(self, etype, dt, payload, lo, hi, thresholds, src_x=None, src_P=None, src_row=None, src_col=None,
+                  counts=False):
+        """Ragged tails of ONE event stream in one launch (kf_run_tails): etype [T] uint8, dt [T]
+        float64, payload [T, 9]; filter f runs the events [lo[f], hi[f]) (host int arrays [B]) with
+        run_sweep's event step against thresholds[f], from row src_row[f], column src_col[f] of
+        src_x [R, n, Bs] / src_P [R, rows, Bs] (run_sweep's ckpt_x / ckpt_P as they are) or, with
+        src_row[f] = -1 (the default for every tail), from its own state in the handle.  No
+        records: the end states are state() / status().  Returns n_updated [B] int32 if ``counts``
+        else None.  A wave carries 8 tails and runs to its longest: sort the tails by length."""
+        if self.model not in REF_MODELS:
+            raise ValueError('run_tails needs a ref15 or ref8 handle')
+        T, B = int(etype.shape[0]), self.batch
+        et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
+        dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
+        pay = self._dev(payload.reshape(T, 9), (T, 9), 'payload')
+        thr = self._dev(thresholds, (B,), 'thresholds', torch.float64)
+
+        def host(a, name, fill):
+            a = np.full(B, fill, np.int32) if a is None else np.ascontiguousarray(a, dtype=np.int32)
+            if a.shape != (B,):
+                raise ValueError(f'{name}: shape {a.shape} != expected {(B,)}')
+            return a
+
+        lo_h, hi_h = host(lo, 'lo', 0), host(hi, 'hi', 0)
+        row_h, col_h = host(src_row, 'src_row', -1), host(src_col, 'src_col', 0)
+        if (src_x is None) != (src_P is None):
+            raise ValueError('give src_x and src_P together')
+        R = Bs = 0
+        sx = sP = None
+        if src_x is not None:
+            if (src_x.ndim != 3 or src_P.ndim != 3 or src_P.shape[0] != src_x.shape[0]
+                    or src_P.shape[2] != src_x.shape[2]):
+                raise ValueError(f'src_x {tuple(src_x.shape)} / src_P {tuple(src_P.shape)}: expected [R, n, Bs] / '
+                                 f'[R, rows, Bs]')
+            R, Bs = int(src_x.shape[0]), int(src_x.shape[2])
+            sx = self._dev(src_x, (R, self.n, Bs), 'src_x')
+            sP = self._dev(src_P, (R, self.ntri, Bs), 'src_P')
+        nu = torch.zeros(B, dtype=torch.int32, device=self.device) if counts else None
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        check(_lib.lib().kf_run_tails(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), as_p(lo_h), as_p(hi_h), _ptr(thr),
+                                      _ptr(sx) if R and Bs else None, _ptr(sP) if R and Bs else None, R, Bs,
+                                      as_p(row_h), as_p(col_h), _ptr(nu), self._stream()))
+        return nu
+
     def stream_check(self):
         """The checks of the last run_stream (kf_stream_check; synchronises the stream)."""
         out = (ctypes.c_double * 8)()

@@ -24,6 +24,9 @@ import torch
 from . import _lib, ingest, ref15
 from .ref15 import from_blocks
 
+# the experiment loop's r_value ratios (kf_workers.py:2303): R_threshold = ratio x the lowest log-det
+RATIOS = (0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8)
+
 __all__ = ['KF_SensorFusion', 'Scheduler', 'evaluate_combo_chunk_worker', 'find_start_idx_for_time_offset']
 
 
@@ -496,7 +499,8 @@ class KF_SensorFusion:
         ``indexed_sensor_data`` — full, adaptive and no-update filters and the brute-force search.
         The warm starts are ``initial_pts`` / ``initial_states`` (P and states[-1] of each
         window's warm-up), or come from ``sweep`` (an AdaptiveSweep, run_adaptive_threshold_sweep)
-        as sweep.warm_start(sweep_index[w], start_idxs[w]).  ``ratios``: each window's R_threshold
+        as sweep.warm_starts(sweep_index, start_idxs), every window's tail in one launch.
+        ``ratios``: each window's R_threshold
         is ratios[w] times its full filter's lowest log-det, as the loop rescales its r_value
         (:2325); ``thresholds``: R_threshold per window, as given.  Returns the WindowBatch, a
         sequence of per-window dicts ('full', 'adaptive', 'no_update', 'brute_force',
@@ -505,7 +509,7 @@ class KF_SensorFusion:
         if sweep is not None:
             if sweep_index is None:
                 raise ValueError('sweep needs sweep_index: each window\'s threshold of the sweep')
-            warm = [sweep.warm_start(int(i), s) for i, s in zip(sweep_index, starts)]
+            warm = sweep.warm_starts([int(i) for i in sweep_index], starts)
             if any(w is None for w in warm):
                 raise ValueError('the sweep has no warm start for some window (no fix before its start)')
             initial_states = [w[0] for w in warm]
@@ -515,6 +519,21 @@ class KF_SensorFusion:
         return ref15.run_window_batch(self.indexed_sensor_data, starts, [s + int(window) for s in starts], initial_pts,
                                       initial_states, ratios=ratios, thresholds=thresholds, k_max=k_max,
                                       dtype=self.dtype, device=self.device, consts=self._consts())
+
+    def run_experiment_grid(self, start_idxs, sweep, window=25, ratios=RATIOS, k_max=4):
+        """Every start point under every threshold of ``sweep`` (an AdaptiveSweep over the loop's
+        thresholds lb x ratios, :2301-2317): the len(start_idxs) x len(ratios) windows
+        [s, s + window), start-major (window w = start w // len(ratios) under threshold
+        w % len(ratios)), each warm-started by the sweep under its own threshold and rescaled by
+        its own ratio (:2325).  One sweep.warm_starts call and one ref15.run_window_batch.
+        Returns the WindowBatch."""
+        ratios = [float(r) for r in ratios]
+        if len(ratios) != len(sweep.thresholds):
+            raise ValueError(f'{len(ratios)} ratios for the sweep\'s {len(sweep.thresholds)} thresholds')
+        points = [int(s) for s in start_idxs]
+        starts = [s for s in points for _ in ratios]
+        return self.run_experiment_windows(starts, window=window, ratios=ratios * len(points), sweep=sweep,
+                                           sweep_index=list(range(len(ratios))) * len(points), k_max=k_max)
 
     def run_dead_reckoning_for_IMU(self):
         return []  # the reference's body is commented out and returns an empty list (kf_workers.py:1394-1425)

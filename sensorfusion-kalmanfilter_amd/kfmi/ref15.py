@@ -591,7 +591,8 @@ class AdaptiveSweep:
     for thresholds[i] (needs records=True).  ``warm_start(i, end_idx)``: (states[-1], P,
     previous_time) of the driver over [start_idx, end_idx), from the checkpoint at or before
     end_idx (every ``checkpoint_every`` array entries) and a one-filter sweep over the fewer than
-    checkpoint_every events after it."""
+    checkpoint_every events after it.  ``warm_starts(index, end_idxs)``: the list of
+    warm_start(index[w], end_idxs[w]), every tail in one launch (kf_run_tails)."""
 
     def __init__(self, events, thresholds, start_idx=None, end_idx=None, initial_pt=None, initial_state=None,
                  dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096):
@@ -601,6 +602,7 @@ class AdaptiveSweep:
         self.every = int(checkpoint_every)
         self.n_updates = np.zeros(len(self.thresholds), np.int64)
         self.empty = True  # a cold window without a fix: the driver returns None
+        self._kf1, self._kft = None, {}  # warm_start's one-filter handle; warm_starts' handles by batch size
         B = len(self.thresholds)
         ds = _device_stream(events)
         n = len(ds) if ds is not None else len(events)
@@ -690,6 +692,9 @@ class AdaptiveSweep:
         if getattr(self, '_kf1', None) is not None:
             self._kf1.close()
             self._kf1 = None
+        for kf in getattr(self, '_kft', {}).values():
+            kf.close()
+        self._kft = {}
 
     def __del__(self):
         try:
@@ -743,6 +748,50 @@ class AdaptiveSweep:
         xs = x[:6, 0].double().cpu().numpy()
         prev = float(self._prev[n - 1])
         return (prev, *xs.tolist()), from_blocks(Pb[:, 0].double().cpu().numpy()), prev
+
+    def warm_starts(self, index, end_idxs):
+        """[warm_start(index[w], end_idxs[w]) for every w], the same tuples and Nones, computed
+        at once: every tail past its checkpoint in ONE run_tails launch straight from the
+        sweep's checkpoint arrays (row -1: the sweep's own start state), one device-to-host copy
+        and vectorised host code.  The tails are sorted by length before the launch, so the
+        eight tails of a wave are of similar length (a wave runs to its longest), and the
+        results un-permuted.  One handle per batch size is kept until close()."""
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        W = len(index)
+        if len(end_idxs) != W:
+            raise ValueError(f'warm_starts: {W} thresholds for {len(end_idxs)} end points')
+        out = [None] * W
+        if self.empty or W == 0:
+            return out
+        if W and (index.min() < 0 or index.max() >= len(self.thresholds)):
+            raise IndexError(f'warm_starts: threshold index outside [0, {len(self.thresholds)})')
+        ends = np.array([self.end_idx if e is None or e > self.end_idx else int(e) for e in end_idxs], dtype=np.int64)
+        valid = np.nonzero(ends > self.start_off)[0] if self.cold else np.arange(W)
+        if len(valid) == 0:
+            return out
+        n = 1 + np.maximum(ends[valid] - self.start_off, 0)  # array entries of each prefix
+        row = n // self.every - 1 if self.every > 0 else np.full(len(valid), -1, np.int64)
+        lo = np.where(row >= 0, (row + 1) * self.every, 0)
+        order = np.argsort(n - lo, kind='stable')
+        sel = valid[order]
+        B = len(sel)
+        kf = self._kft.get(B)
+        if kf is None:
+            kf = self._kft[B] = BatchedKF('ref15', B, self.dtype, device=self.dev.index or 0,
+                                          params=_params(self.consts))
+        if (row < 0).any():
+            kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
+        kf.run_tails(self._et, self._dt, self._pay, lo[order], n[order], torch.from_numpy(self.thresholds[index[sel]]),
+                     src_x=self._cx if self.every > 0 else None, src_P=self._cP if self.every > 0 else None,
+                     src_row=row[order], src_col=index[sel])
+        x, Pb = kf.state()
+        host = torch.cat([x[:6], Pb]).double().cpu().numpy()  # [6 + 27, B]
+        xs = host[:6].T.tolist()
+        Ps = from_blocks(np.ascontiguousarray(host[6:].T))
+        prev = self._prev[n[order] - 1].tolist()
+        for j, w in enumerate(sel.tolist()):
+            out[w] = ((prev[j], *xs[j]), Ps[j], prev[j])
+        return out
 
 
 def run_adaptive_threshold_sweep(events, thresholds, **kw):
