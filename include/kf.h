@@ -31,13 +31,13 @@
  * All functions return KF_OK (0) or a negative KF_E* code; kf_last_error() then
  * describes the failure (thread-local).  Launching entry points are asynchronous on
  * the given hipStream_t (NULL = the null stream) and never synchronise, so they can be
- * captured into a hipGraph.  Workspaces: kf_search_combos, kf_search_windows, kf_run_stream,
- * kf_run_tails and kf_run_scheduled(_rec) keep a device workspace in the handle, allocated by
+ * captured into a hipGraph.  Workspaces: kf_search_combos, kf_search_windows, kf_search_schedules,
+ * kf_run_stream, kf_run_tails and kf_run_scheduled(_rec) keep a device workspace in the handle, allocated by
  * the first call that needs it and grown (hipMalloc; hipFree synchronises the device) only by a call that
  * needs more than every earlier one; every other launch allocates nothing.  Run such a call
  * once eagerly before capturing it: inside a capture nothing is allocated (kf_run_scheduled
- * then takes its fused kernel, kf_run_stream and kf_run_tails return KF_EINVAL; kf_search_combos
- * and kf_search_windows synchronise and are never captured).  A workspace a capture used
+ * then takes its fused kernel, kf_run_stream and kf_run_tails return KF_EINVAL; kf_search_combos,
+ * kf_search_windows and kf_search_schedules synchronise and are never captured).  A workspace a capture used
  * is never freed before kf_free, so a graph stays valid after a later, larger eager call: each
  * such growth keeps the smaller buffer (retired) until kf_free or kf_release_retired, so a
  * handle that alternates captures with ever-larger eager calls holds all of them.
@@ -520,6 +520,64 @@ int kf_search_windows(kf_batch* handle, int W, int n_max, const int32_t* n_event
                       const double* init, const double* prev_time, const double* target_end,
                       const double* threshold, int k_max, uint64_t* winner, int32_t* k_found,
                       uint64_t* n_accepted, void* stream);
+
+/* KF_MODEL_REF15, f64: the per-window schedule search scored by position RMSE, the notebook's
+ * run_brute_force_kalman_filter (KF_SensorFusion.ipynb, with its calculate_accuracy_metrics).
+ * A slice of the log is cut into W sampling windows; a schedule picks one candidate event from
+ * every window, and every schedule (itertools.product over the windows' queues) is its own
+ * 15-state filter.  An f32 or other-model handle is KF_EINVAL.  The handle's constants apply
+ * (kf_params.ref_*); its batch size is not used.
+ * Inputs, all HOST arrays (uploaded through a handle workspace): q_len [W] candidates per window,
+ * each >= 1; events [C][11] doubles (t, KF_EVENT_GPS | KF_EVENT_IMU, payload[9]), queue after
+ * queue, C = sum q_len; ref_pos [C][3] the reference position at each candidate's time; init [42]
+ * (x, block-packed P); prev_time the time of init, NaN = none yet: the first pick's dt is 0 (the
+ * notebook's `prev_time is None`).
+ * The filter of a schedule (one digit c_w in [0, q_len[w]) per window) starts from init and, for
+ * w = 0 .. W - 1, predicts over dt = t[pick_w] - t[pick_{w-1}] and applies the pick's GPS or IMU
+ * update, exactly as kf_run_events does an event without a gate.  After each update
+ * sse += sum_{axis < 3} (x[axis] - ref_pos[pick_w][axis])^2, axes in order, windows in order, and
+ * metric = sqrt(sse / W), W counting the fixed windows too.  The score reads the position only
+ * and P is block-diagonal over the axis chains, so only the three (pos, vel, acc) chains are
+ * run: init's attitude and rate entries are not read, and a NaN in an IMU candidate's attitude
+ * or rate payload does not reach the metric (kf_run_events keeps it within those chains too).
+ * A schedule's rank is its position in itertools.product order over the FREE windows (the last
+ * window varies fastest), in 64 bits.  The schedule with the smallest metric wins, ties go to
+ * the smallest rank (the notebook's `metric < best_metric`); a NaN or +inf metric never wins.
+ * Host outputs: *best_rank, *best_metric (UINT64_MAX and +inf if no metric is < +inf),
+ * *n_valid = the schedules with metric < +inf.  The result is the same on every run: the
+ * reduction is an exact lexicographic min of (metric bits, rank), no floating-point atomics.
+ * n_fixed / fixed [n_fixed]: the first n_fixed windows' digits are fixed[] and the call searches
+ * the rest (0 <= n_fixed <= W; n_fixed = W scores the one schedule): the host splits a search
+ * too large for one call into such classes, as n_fixed / fixed_mask do for kf_search_combos.
+ * metric_out: device [N_free] doubles (nullable) receives every searched schedule's metric at
+ * its free rank; the classes of one search fill one buffer through offset pointers.
+ * Time order, a departure from the notebook: every candidate of window w + 1 must be no earlier
+ * than every candidate of window w, and no candidate earlier than a finite prev_time; otherwise
+ * KF_EINVAL naming the window, before anything is queued.  (The notebook has no dt < 0 guard and
+ * would predict over the negative step; its own windowing never produces one from a sorted log.)
+ * Limits, each KF_EINVAL and never clamped or wrapped: 1 <= W <= 64; 1 <= q_len[w] <= 1024;
+ * N_free = prod of the free windows' q_len < 2^40; the widest stored level (the product of the
+ * free windows' q_len but the last) <= 2^26 nodes; finite candidate times; types GPS or IMU;
+ * fixed[w] in [0, q_len[w]).
+ * One launch per free window: level j holds the prefixes over the first j + 1 free windows, one
+ * lane per node, a node (9 states, 18 covariance entries, the running sse: 28 doubles) advanced
+ * from its parent by one event step; the last level is never stored.  The workspace is two
+ * buffers of the widest stored level plus the inputs (kf_schedule_plan), kept in the handle and
+ * grown on demand ("Workspaces" above).  The call synchronises `stream` (the results return
+ * through a mapped host buffer of the handle): inside a graph capture it returns KF_EINVAL. */
+int kf_search_schedules(kf_batch* handle, int W, const int32_t* q_len, const double* events, const double* ref_pos,
+                        const double* init, double prev_time, int n_fixed, const int32_t* fixed,
+                        uint64_t* best_rank, double* best_metric, uint64_t* n_valid, void* metric_out, void* stream);
+
+/* How kf_search_schedules would run W windows of q_len [W] candidates with the first n_fixed
+ * fixed, without running it (no device work): out[0] = N_free, the schedules the call searches
+ * (-1 if N_free >= 2^40, which the search refuses), out[1] = the widest stored level's nodes (0
+ * with fewer than two free windows; the search refuses more than 2^26), out[2] = the workspace
+ * bytes (two level buffers of 28 doubles per node, the candidates, 96 KiB of partials;
+ * INT64_MAX beyond 2^50 nodes).  The plan depends on the queue lengths alone, so `handle` may
+ * be NULL; a handle that is given must be one kf_search_schedules accepts.  W and q_len are
+ * checked as there.  The host uses it to choose n_fixed (kfmi.ref15.search_schedules). */
+int kf_schedule_plan(const kf_batch* handle, int W, const int32_t* q_len, int n_fixed, int64_t* out);
 
 /* How kf_search_combos would run with these arguments, without running it (no device work):
  * out[0] = 1 if axis-symmetric (KF_OPT_AXIS_SYM and init's axis blocks equal bit for bit),

@@ -88,6 +88,14 @@ struct kf_batch {
     size_t tails_ws_bytes;
     bool tails_ws_graph;
     std::vector<kfmi::TailSpec> tails_host;  // the table's host image: it outlives the call that uploads it
+    // kf_search_schedules: device workspace (candidates, init, fixed picks, partials, two level
+    // buffers; grown on demand) and the mapped host buffer its finish kernel writes the result to
+    void* sch_ws;
+    size_t sch_ws_bytes;
+    bool sch_ws_graph;               // never set (the call is not capturable); grow_ws' interface
+    uint64_t* sch_host;
+    uint64_t* sch_host_dev;
+    std::vector<double> sch_cand;    // the candidates' host image [14][C]
 };
 
 namespace {
@@ -632,6 +640,8 @@ int kf_free(kf_batch* h) {
     if (h->kc) (void)hipFree(h->kc);
     if (h->sched_ws) (void)hipFree(h->sched_ws);
     if (h->tails_ws) (void)hipFree(h->tails_ws);
+    if (h->sch_ws) (void)hipFree(h->sch_ws);
+    if (h->sch_host) (void)hipHostFree(h->sch_host);
     for (auto& r : h->retired) (void)hipFree(r.first);
     delete h;
     return KF_OK;
@@ -1821,6 +1831,193 @@ int kf_search_windows(kf_batch* h, int W, int n_max, const int32_t* n_events, co
         k_found[w] = static_cast<int32_t>(r[1]);
         if (n_accepted)
             for (int k = 0; k <= k_max; ++k) n_accepted[size_t(w) * size_t(k_max + 1) + k] = r[2 + k];
+    }
+    return KF_OK;
+}
+
+namespace {
+// The shape of a schedule search: free schedules (saturated at 2^62), the widest stored level's
+// nodes (the free windows' prefix products but the last; 0 with fewer than two free windows),
+// candidates in all, and the workspace layout.
+struct SchedulePlan {
+    uint64_t n_free, widest, C;
+    size_t cand_b, init_b, fix_b, part_b, level_b;  // level_b: one of the two level buffers
+    int64_t bytes;                                  // the whole workspace (INT64_MAX: beyond any memory)
+};
+int schedule_plan(const char* who, int W, const int32_t* q_len, int n_fixed, SchedulePlan& p) {
+    if (W < 1 || W > kfmi::kScheduleMaxWindows)
+        return fail(KF_EINVAL, "%s: W = %d outside [1, %d]", who, W, kfmi::kScheduleMaxWindows);
+    if (!q_len) return fail(KF_EINVAL, "%s: null q_len", who);
+    if (n_fixed < 0 || n_fixed > W) return fail(KF_EINVAL, "%s: n_fixed = %d outside [0, W = %d]", who, n_fixed, W);
+    constexpr uint64_t kSat = uint64_t(1) << 62;
+    p = SchedulePlan{};
+    p.n_free = 1;
+    for (int w = 0; w < W; ++w) {
+        if (q_len[w] < 1 || q_len[w] > kfmi::kScheduleMaxQueue)
+            return fail(KF_EINVAL, "%s: q_len[%d] = %d outside [1, %d]", who, w, q_len[w], kfmi::kScheduleMaxQueue);
+        p.C += uint64_t(q_len[w]);
+        if (w < n_fixed) continue;
+        if (w == W - 1 && w > n_fixed) p.widest = p.n_free;
+        p.n_free = p.n_free > kSat / uint64_t(q_len[w]) ? kSat : p.n_free * uint64_t(q_len[w]);
+    }
+    p.cand_b = align256(sizeof(double) * 14 * size_t(p.C));
+    p.init_b = align256(sizeof(double) * 42);
+    p.fix_b = align256(sizeof(int32_t) * size_t(W));
+    p.part_b = align256(sizeof(uint64_t) * 3 * kfmi::kScheduleGrid);
+    if (p.widest > (uint64_t(1) << 50)) {
+        p.level_b = 0;
+        p.bytes = INT64_MAX;
+    } else {
+        p.level_b = align256(sizeof(double) * kfmi::kScheduleRows * size_t(p.widest));
+        p.bytes = int64_t(p.cand_b + p.init_b + p.fix_b + p.part_b + 2 * p.level_b);
+    }
+    return KF_OK;
+}
+int schedule_handle(const kf_batch* h, const char* who) {
+    if (!is_ref15(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 handle", who);
+    if (h->dtype != KF_F64) return fail(KF_EINVAL, "%s: needs an f64 handle (the schedule search has no f32 kernels)", who);
+    return KF_OK;
+}
+}  // namespace
+
+int kf_schedule_plan(const kf_batch* h, int W, const int32_t* q_len, int n_fixed, int64_t* out) {
+    const char* who = "kf_schedule_plan";
+    if (h)
+        if (int rc = schedule_handle(h, who)) return rc;
+    if (!out) return fail(KF_EINVAL, "%s: null output", who);
+    SchedulePlan p;
+    if (int rc = schedule_plan(who, W, q_len, n_fixed, p)) return rc;
+    out[0] = p.n_free >= kfmi::kScheduleMaxFree ? -1 : int64_t(p.n_free);
+    out[1] = int64_t(p.widest);
+    out[2] = p.bytes;
+    return KF_OK;
+}
+
+int kf_search_schedules(kf_batch* h, int W, const int32_t* q_len, const double* events, const double* ref_pos,
+                        const double* init, double prev_time, int n_fixed, const int32_t* fixed,
+                        uint64_t* best_rank, double* best_metric, uint64_t* n_valid, void* metric_out, void* stream) {
+    const char* who = "kf_search_schedules";
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = schedule_handle(h, who)) return rc;
+    SchedulePlan p;
+    if (int rc = schedule_plan(who, W, q_len, n_fixed, p)) return rc;
+    if (!events || !ref_pos || !init) return fail(KF_EINVAL, "%s: null events/ref_pos/init", who);
+    if (!best_rank || !best_metric || !n_valid) return fail(KF_EINVAL, "%s: null best_rank/best_metric/n_valid", who);
+    if (n_fixed > 0 && !fixed) return fail(KF_EINVAL, "%s: null fixed with n_fixed = %d", who, n_fixed);
+    if (p.n_free >= kfmi::kScheduleMaxFree)
+        return fail(KF_EINVAL, "%s: the free windows hold 2^40 schedules or more; fix more windows (n_fixed) and split the call",
+                    who);
+    if (p.widest > kfmi::kScheduleMaxNodes)
+        return fail(KF_EINVAL, "%s: the widest stored level has %llu nodes, more than %llu; fix more windows (n_fixed)", who,
+                    static_cast<unsigned long long>(p.widest), static_cast<unsigned long long>(kfmi::kScheduleMaxNodes));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (capturing(st)) return fail(KF_EINVAL, "%s: not capturable (its results return to the host in the call)", who);
+    // the candidates, window after window: types, finite times, and the windows in time order
+    const int C = int(p.C);
+    std::vector<int32_t> off(size_t(W) + 1, 0), fix_idx(static_cast<size_t>(W), 0);
+    double hi_before = prev_time;  // NaN: nothing to compare with yet
+    for (int w = 0; w < W; ++w) {
+        off[size_t(w) + 1] = off[size_t(w)] + q_len[w];
+        double lo = 0.0, hi = 0.0;
+        for (int i = 0; i < q_len[w]; ++i) {
+            const double* e = events + size_t(off[size_t(w)] + i) * 11;
+            if (e[1] != KF_EVENT_GPS && e[1] != KF_EVENT_IMU)
+                return fail(KF_EINVAL, "%s: window %d candidate %d has type %g (GPS=0 or IMU=1)", who, w, i, e[1]);
+            if (!std::isfinite(e[0])) return fail(KF_EINVAL, "%s: window %d candidate %d has time %g", who, w, i, e[0]);
+            lo = i ? std::min(lo, e[0]) : e[0];
+            hi = i ? std::max(hi, e[0]) : e[0];
+        }
+        if (lo < hi_before)  // false for a NaN prev_time
+            return w ? fail(KF_EINVAL, "%s: window %d has a candidate at %.9g, earlier than window %d's latest (%.9g)", who,
+                            w, lo, w - 1, hi_before)
+                     : fail(KF_EINVAL, "%s: window 0 has a candidate at %.9g, earlier than prev_time (%.9g)", who, lo,
+                            hi_before);
+        hi_before = hi;
+        if (w < n_fixed) {
+            if (fixed[w] < 0 || fixed[w] >= q_len[w])
+                return fail(KF_EINVAL, "%s: fixed[%d] = %d outside [0, q_len = %d)", who, w, fixed[w], q_len[w]);
+            fix_idx[size_t(w)] = off[size_t(w)] + fixed[w];
+        }
+    }
+    const size_t need = size_t(p.bytes);
+    if (!grow_ws(h, &h->sch_ws, &h->sch_ws_bytes, &h->sch_ws_graph, need, st))
+        return fail(KF_ENOMEM, "%s: hipMalloc of %zu bytes of workspace failed", who, need);
+    if (!h->sch_host) {
+        void* hp = nullptr;
+        if (hipHostMalloc(&hp, sizeof(uint64_t) * 4, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(KF_ENOMEM, "%s: hipHostMalloc of the result buffer failed", who);
+        }
+        void* pd = nullptr;
+        if (hipHostGetDevicePointer(&pd, hp, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(hp);
+            return fail(KF_EHIP, "%s: no device address for the result buffer", who);
+        }
+        h->sch_host = static_cast<uint64_t*>(hp);
+        h->sch_host_dev = static_cast<uint64_t*>(pd);
+    }
+    // candidates as rows [14][C] (t, type, payload[9], ref_pos[3]): lanes with neighbouring picks
+    // read neighbouring elements.  The image lives in the handle until the next call replaces it,
+    // after this call's synchronisation.
+    h->sch_cand.assign(size_t(14) * size_t(C), 0.0);
+    for (int i = 0; i < C; ++i) {
+        for (int r = 0; r < 11; ++r) h->sch_cand[size_t(r) * size_t(C) + size_t(i)] = events[size_t(i) * 11 + size_t(r)];
+        for (int r = 0; r < 3; ++r) h->sch_cand[size_t(11 + r) * size_t(C) + size_t(i)] = ref_pos[size_t(i) * 3 + size_t(r)];
+    }
+    char* dw = static_cast<char*>(h->sch_ws);
+    double* d_cand = reinterpret_cast<double*>(dw);
+    double* d_init = reinterpret_cast<double*>(dw + p.cand_b);
+    int32_t* d_fix = reinterpret_cast<int32_t*>(dw + p.cand_b + p.init_b);
+    uint64_t* d_part = reinterpret_cast<uint64_t*>(dw + p.cand_b + p.init_b + p.fix_b);
+    double* level[2] = {reinterpret_cast<double*>(dw + p.cand_b + p.init_b + p.fix_b + p.part_b),
+                        reinterpret_cast<double*>(dw + p.cand_b + p.init_b + p.fix_b + p.part_b + p.level_b)};
+    hipError_t e = hipMemcpyAsync(d_cand, h->sch_cand.data(), sizeof(double) * 14 * size_t(C), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_init, init, sizeof(double) * 42, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_fixed > 0)
+        e = hipMemcpyAsync(d_fix, fix_idx.data(), sizeof(int32_t) * size_t(n_fixed), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e, "kf_search_schedules: upload");
+    kfmi::ScheduleArgs a{};
+    a.W = W;
+    a.n_fixed = n_fixed;
+    a.C = C;
+    a.cand = d_cand;
+    a.init = d_init;
+    a.fixed_idx = d_fix;
+    a.prev_time = prev_time;
+    a.partials = d_part;
+    a.kc = h->kc;
+    uint64_t nodes = 1;
+    unsigned leaf_grid = 1;
+    const int n_free_windows = W - n_fixed;
+    for (int j = 0; j < std::max(n_free_windows, 1) && e == hipSuccess; ++j) {
+        const int w = n_fixed + j;
+        const bool leaf = j >= n_free_windows - 1;
+        a.first = j == 0;
+        a.q = n_free_windows ? q_len[w] : 0;
+        a.off = n_free_windows ? off[size_t(w)] : 0;
+        a.q_par = j ? q_len[w - 1] : 0;
+        a.off_par = j ? off[size_t(w) - 1] : 0;
+        nodes *= uint64_t(a.q ? a.q : 1);
+        a.n_nodes = nodes;
+        a.par = j ? level[(j - 1) & 1] : nullptr;
+        a.child = leaf ? nullptr : level[j & 1];
+        a.metric_out = leaf ? static_cast<double*>(metric_out) : nullptr;
+        if (leaf) leaf_grid = kfmi::schedule_grid(nodes);
+        e = kfmi::launch_ref15_schedule(a, leaf, st);
+    }
+    if (e != hipSuccess) return hip_fail(e, "kf_search_schedules: launch");
+    e = kfmi::launch_schedule_finish(d_part, int(leaf_grid), h->sch_host_dev, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "kf_search_schedules: results");
+    const uint64_t key = h->sch_host[0];
+    *n_valid = h->sch_host[2];
+    if (h->sch_host[2] == 0) {
+        *best_rank = UINT64_MAX;
+        *best_metric = HUGE_VAL;
+    } else {
+        *best_rank = h->sch_host[1];
+        std::memcpy(best_metric, &key, sizeof key);
     }
     return KF_OK;
 }

@@ -326,6 +326,52 @@ struct Ref15WindowArgs {
 constexpr int kSearchWindowSlots = 16;   // counters per window and kind (sizes 0 .. 8 used)
 constexpr int kSearchWindowsMaxK = 8;
 
+// Schedule search (kf_search_schedules): one pick per sampling window, every schedule of the
+// product of the windows' queues its own filter, scored by the position RMSE of its trajectory
+// (KF_SensorFusion.ipynb's run_brute_force_kalman_filter).  Level j holds the prod_{i <= j} q_i
+// prefixes of the free windows in product order (the last window fastest); node r's parent is
+// r / q_j and its pick candidate r % q_j of that window.  One launch per level, one lane per
+// node.  A node is kScheduleRows doubles, SoA [row][nodes]: the 9 states and 18 covariance
+// entries of the three (pos, vel, acc) chains (the score reads the position only, and P is
+// block-diagonal over the chains, so the attitude chains are not carried) and the running sum
+// of squared position errors.  The last level is never stored: its lanes finish the metric in
+// registers and reduce (metric, rank) to one partial per workgroup.
+struct ScheduleArgs {
+    int W;                   // windows, fixed ones included: metric = sqrt(sse / W)
+    int n_fixed;             // first launch: the root walks these picks before its own
+    int first;               // the first launched level: parents are the root (init, prev_time)
+    int q;                   // candidates of this level's window (0: every window is fixed, one lane)
+    int off;                 // its first candidate's column in cand
+    int q_par, off_par;      // the parent level's window (the parent's pick gives the previous time)
+    int C;                   // candidates in all: cand's row length
+    uint64_t n_nodes;        // lanes of this launch
+    const double* cand;      // device [14][C]: t, type, payload[9], ref_pos[3] per candidate
+    const double* init;      // device [42]: x, block-packed P
+    const int32_t* fixed_idx;  // device [n_fixed]: the fixed picks' columns in cand
+    double prev_time;        // time of init (NaN: the first pick's dt is 0)
+    const double* par;       // level j - 1 [kScheduleRows][n_nodes / q] (unused when first)
+    double* child;           // level j [kScheduleRows][n_nodes] (a stored level)
+    double* metric_out;      // the last level: [n_nodes] every schedule's metric, or nullptr
+    uint64_t* partials;      // the last level: [grid][3] (metric bits, rank, finite metrics) per workgroup
+    const RefConsts* kc;     // the handle's noise constants, or nullptr (the reference's)
+};
+constexpr int kScheduleRows = 28;
+constexpr int kScheduleMaxWindows = 64;            // W
+constexpr int kScheduleMaxQueue = 1024;            // candidates per window
+constexpr uint64_t kScheduleMaxNodes = uint64_t(1) << 26;  // widest stored level
+constexpr uint64_t kScheduleMaxFree = uint64_t(1) << 40;   // schedules per call
+constexpr unsigned kScheduleGrid = 4096;           // workgroups of a level launch at most (lanes stride over the nodes)
+inline unsigned schedule_grid(uint64_t n_nodes) {
+    const uint64_t b = (n_nodes + 255) / 256;
+    return unsigned(b < kScheduleGrid ? (b ? b : 1) : kScheduleGrid);
+}
+// one level of a schedule search (leaf: the last one, which scores instead of storing)
+hipError_t launch_ref15_schedule(const ScheduleArgs& a, bool leaf, hipStream_t stream);
+// the last level's `n` workgroup partials reduced to host[0..2] (the device address of mapped
+// host memory): the smallest finite metric's bits, the smallest rank that holds it, the number
+// of finite metrics; (UINT64_MAX, UINT64_MAX, 0) when no metric is finite
+hipError_t launch_schedule_finish(const uint64_t* partials, int n, uint64_t* host, hipStream_t stream);
+
 // T rows of a search node: the block-packed P (27) and the running max's mantissa; an
 // axis-symmetric search (Ref15SearchArgs::sym) keeps one pva block and one aw block (6 + 3) and
 // the mantissa; then 4 B of exponent, 8 B of time and 8 B of mask per node

@@ -122,7 +122,10 @@ SIGNATURES = {
     'kf_search_combos': (_i, [_vp, _i, _vp, _vp, _d, _d, _d, _i, _i, _i, ctypes.c_uint64,
                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_i), _vp, _vp, _vp]),
     'kf_search_windows': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    'kf_search_plan': (_i, [_vp, _i, _vp, _i, ctypes.c_uint64, _i, _vp]),
+    'kf_search_schedules': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _i, _vp, ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.POINTER(_d), ctypes.POINTER(ctypes.c_uint64), _vp, _vp]),
+    'kf_schedule_plan': (_i, [_vp, _i, _vp, _i, _vp]),
+    'kf_search_plan': (_i,[_vp, _i, _vp, _i, ctypes.c_uint64, _i, _vp]),
     'kf_search_info': (_i, [_vp, _vp]),
     'kf_score_candidates': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
     'kf_score_rows': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),

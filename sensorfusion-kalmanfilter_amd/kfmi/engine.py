@@ -8,6 +8,7 @@ allocator / stream provider here); all arithmetic happens in the HIP kernels.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -591,6 +592,58 @@ class BatchedKF:
                                            th.ctypes.data_as(vp), k_max, win.ctypes.data_as(vp),
                                            kf.ctypes.data_as(vp), acc.ctypes.data_as(vp), self._stream()))
         return kf, win, acc
+
+    def search_schedules(self, events, q_len, ref_pos, init, prev_time=float('nan'), fixed=(), metrics=False):
+        """The per-window schedule search scored by position RMSE (kf_search_schedules; the
+        handle's batch size is not used).  events: host [C, 11] float64 (t, type, payload[9]), the
+        windows' queues one after another, q_len [W] their lengths; ref_pos [C, 3] the reference
+        position at each candidate's time; init [42] (x, block-packed P); prev_time the time of
+        init (NaN: the first pick's dt is 0).  ``fixed``: the digits of the first len(fixed)
+        windows; the rest are searched.  ``metrics``: True for a new device tensor of the N_free
+        metrics in itertools.product order, or a contiguous float64 device tensor of N_free
+        entries to fill (a slice of one search's buffer).  Returns (best_rank or None, the
+        winner's digits over all W windows or None, best_metric, n_valid, metrics or None)."""
+        ev = np.ascontiguousarray(events, dtype=np.float64)
+        ql = np.ascontiguousarray(q_len, dtype=np.int32)
+        rp = np.ascontiguousarray(ref_pos, dtype=np.float64)
+        ini = np.ascontiguousarray(init, dtype=np.float64)
+        fx = np.ascontiguousarray(fixed, dtype=np.int32)
+        if ql.ndim != 1 or fx.ndim != 1 or fx.size > ql.size:
+            raise ValueError('q_len must be [W] and fixed at most W digits')
+        C = int(ql.sum())
+        if ev.shape != (C, 11) or rp.shape != (C, 3) or ini.shape != (42,):
+            raise ValueError(f'events must be [{C}, 11], ref_pos [{C}, 3] and init [42]')
+        W, nf = int(ql.size), int(fx.size)
+        n_free = math.prod(int(q) for q in ql[nf:])
+        if isinstance(metrics, torch.Tensor):
+            mt = metrics
+            if (mt.numel() != n_free or mt.dtype != torch.float64 or mt.device != self.device
+                    or not mt.is_contiguous()):
+                raise ValueError(f'metrics must be a contiguous float64 tensor of {n_free} entries on {self.device}')
+        else:
+            mt = torch.empty(n_free, dtype=torch.float64, device=self.device) if metrics and n_free < 1 << 40 else None
+        rank, best, nv = ctypes.c_uint64(0), ctypes.c_double(0.0), ctypes.c_uint64(0)
+        vp = ctypes.c_void_p
+        check(_lib.lib().kf_search_schedules(self.handle, W, ql.ctypes.data_as(vp), ev.ctypes.data_as(vp),
+                                             rp.ctypes.data_as(vp), ini.ctypes.data_as(vp), float(prev_time), nf,
+                                             fx.ctypes.data_as(vp), ctypes.byref(rank), ctypes.byref(best),
+                                             ctypes.byref(nv), _ptr(mt), self._stream()))
+        if nv.value == 0:
+            return None, None, float('inf'), 0, mt
+        digits, r = [], rank.value
+        for q in reversed(ql[nf:]):
+            digits.append(r % int(q))
+            r //= int(q)
+        return rank.value, tuple(int(d) for d in fx) + tuple(reversed(digits)), best.value, nv.value, mt
+
+    def schedule_plan(self, q_len, n_fixed=0):
+        """How search_schedules would run these windows (kf_schedule_plan, no device work):
+        dict(n_free (None: 2^40 schedules or more), widest, workspace_bytes)."""
+        ql = np.ascontiguousarray(q_len, dtype=np.int32)
+        out = np.zeros(3, dtype=np.int64)
+        check(_lib.lib().kf_schedule_plan(self.handle, int(ql.size), ql.ctypes.data_as(ctypes.c_void_p), int(n_fixed),
+                                          out.ctypes.data_as(ctypes.c_void_p)))
+        return {'n_free': None if out[0] < 0 else int(out[0]), 'widest': int(out[1]), 'workspace_bytes': int(out[2])}
 
     def search_plan(self, init, n, k_max=None, n_fixed=0, fixed_mask=0):
         """How search_combos would run over n candidates (kf_search_plan, no device work):

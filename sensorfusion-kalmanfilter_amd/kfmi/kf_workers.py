@@ -492,6 +492,23 @@ class KF_SensorFusion:
             self.indexed_sensor_data, start_idx, end_idx, R_threshold, initial_pt, initial_state,
             max_combos_in_memory=max_combos_in_memory, dtype=self.dtype, device=self.device, consts=self._consts())
 
+    def run_brute_force_kalman_filter(self, start_idx=0, end_idx=None, overwrite_sampling_freq=None,
+                                      max_combos_in_memory=1000):
+        """The notebook's per-window schedule search (KF_SensorFusion.ipynb,
+        run_brute_force_kalman_filter): one pick per sampling window of 1/f seconds, every
+        schedule its own filter from x = 0 and the notebook's P0, scored by the position RMSE
+        against ``utm_data`` (the event list's own fixes when it is empty), the first schedule
+        with the strictly smallest score returned as the notebook's dict.  With no complete
+        window or no finite score the four best entries are None and accuracy_metric is inf.
+        ``max_combos_in_memory`` is the notebook's argument; the search (ref15.search_schedules)
+        needs no per-schedule batch."""
+        f = overwrite_sampling_freq if overwrite_sampling_freq is not None else self.processing_frequency
+        r = ref15.search_schedules(self.indexed_sensor_data, start_idx, end_idx, f,
+                                   track=self.utm_data if len(self.utm_data) else None, consts=self._consts(),
+                                   device=self.device)
+        return {k: r[k] for k in ('selected_sensors', 'final_state', 'final_covariance', 'trajectory',
+                                  'accuracy_metric')}
+
     def run_experiment_windows(self, start_idxs, window=25, ratios=None, thresholds=None, sweep=None,
                                sweep_index=None, initial_pts=None, initial_states=None, k_max=4):
         """The experiment loop's window phase (kf_workers.py:2320-2345) for every start point at

@@ -13,6 +13,7 @@ the event list (``indexed_sensor_data``, built by combine_sensor_data, kf_worker
     run_no_update_kalman_filter                          kf_workers.py:1060-1160
     scheduler_gain / scheduler_cov_trace (Scheduler)     kf_workers.py:112-185
     sampling_sweep (the driver behind sampling_sweep/kf_plot_{10..120}.png)
+    search_schedules (run_brute_force_kalman_filter)     KF_SensorFusion.ipynb, the class cell
 
 Host code here only selects events and differences their time stamps in fp64 with the
 reference's rules (first-GPS start, negative-dt skips); every predict/update/logdet runs in the
@@ -23,6 +24,7 @@ reference itself produces is, exactly (see csrc/kf_ref15.hip).
 """
 from __future__ import annotations
 
+import itertools
 import math
 
 import numpy as np
@@ -1324,6 +1326,169 @@ def run_brute_force_kalman_filter_no_sampling_min_usage(events, start_idx=0, end
                                   consts=consts, kf=kf)
     finally:
         kf.close()
+
+
+# --------------------------------------------------------------------------------------------
+# The per-window schedule search scored by RMSE (KF_SensorFusion.ipynb's
+# run_brute_force_kalman_filter and calculate_accuracy_metrics)
+# --------------------------------------------------------------------------------------------
+
+# the notebook's cold-start covariance (KF_SensorFusion.ipynb: run_brute_force_kalman_filter's Pt)
+SCHEDULE_P0 = np.diag([1000.0] * 3 + [100.0] * 9 + [1000.0] * 3)
+SCHEDULE_MAX_NODES = 1 << 26  # kf_internal.h kScheduleMaxNodes: the widest stored level of one call
+
+
+def schedule_queues(events, start_idx=0, end_idx=None, frequency=None):
+    """The notebook's windowing of events[start_idx:end_idx] into sampling windows of 1/frequency
+    seconds: start at the first fix; an event closer than 1/f to the previous trigger is queued;
+    the first event past the window (the trigger) closes the queue and is itself dropped, unless
+    the queue was empty, when it is queued alone; the trailing partial queue is discarded.
+    ``events``: the reference's event list or a kf_workers.EventList.  Returns the list of
+    queues, each a list of event tuples."""
+    if frequency is None or not frequency > 0:
+        raise ValueError('frequency must be > 0')
+    if end_idx is None:
+        end_idx = len(events)
+    period = 1 / frequency
+    queues, queue = [], []
+    started, previous = False, None
+    for ev in events[start_idx:end_idx]:
+        _, stype, t, _ = ev
+        if not started and stype == 'GPS':
+            started, previous = True, t
+        if not started:
+            continue
+        if t - previous < period:
+            queue.append(ev)
+            continue
+        if not queue:
+            queue.append(ev)
+        queues.append(queue)
+        queue = []
+        previous = t
+    return queues
+
+
+def track_positions(track_t, track_p, tq):
+    """Positions of the track (times [G] strictly increasing, positions [G, 3]) at the times tq,
+    linearly interpolated, and extrapolated from the end segments, in fp64, with
+    scipy.interpolate.interp1d(kind='linear', fill_value='extrapolate')'s own formula."""
+    t = np.asarray(track_t, np.float64)
+    p = np.asarray(track_p, np.float64)
+    tq = np.atleast_1d(np.asarray(tq, np.float64))
+    if t.ndim != 1 or t.size < 2 or p.shape != (t.size, 3):
+        raise ValueError('the track needs times [G] and positions [G, 3] with G >= 2')
+    if not np.all(np.diff(t) > 0):
+        raise ValueError('the track\'s times must be strictly increasing')
+    hi = np.clip(np.searchsorted(t, tq, side='left'), 1, t.size - 1)
+    lo = hi - 1
+    slope = (p[hi] - p[lo]) / (t[hi] - t[lo])[:, None]
+    return slope * (tq - t[lo])[:, None] + p[lo]
+
+
+def _track_of(events, track):
+    """(times, positions) of a metric track: a (times, positions) pair, a utm_data list of fix
+    dicts, or None for the event list's own fixes."""
+    if track is None:
+        h = getattr(events, 'h', None)
+        if h is not None:  # an EventList: its stream's host arrays
+            g = np.asarray(h['etype']) == GPS
+            return np.asarray(h['t'], np.float64)[g], np.asarray(h['payload'], np.float64)[g][:, 0:3]
+        track = [sd for _, stype, _, sd in events if stype == 'GPS']
+    if isinstance(track, tuple) and len(track) == 2:
+        return np.asarray(track[0], np.float64), np.asarray(track[1], np.float64)
+    tt = np.array([sd['time'] for sd in track], np.float64)
+    pp = np.array([[sd['easting'], sd['northing'], sd['altitude']] for sd in track], np.float64).reshape(len(tt), 3)
+    return tt, pp
+
+
+def schedule_arrays(queues, track_t, track_p):
+    """The queues as kf_search_schedules' host arrays: (q_len [W] int32, events [C, 11],
+    ref_pos [C, 3])."""
+    flat = [ev for q in queues for ev in q]
+    ev = np.zeros((len(flat), 11))
+    for i, (_, stype, t, sdata) in enumerate(flat):
+        ev[i, 0] = t
+        ev[i, 1] = GPS if stype == 'GPS' else IMU
+        ev[i, 2:] = event_payload(stype, sdata)
+    ref = track_positions(track_t, track_p, ev[:, 0]) if len(flat) else np.zeros((0, 3))
+    return np.array([len(q) for q in queues], np.int32), ev, ref
+
+
+def search_schedules(events, start_idx=0, end_idx=None, frequency=None, initial_pt=None, initial_state=None,
+                     track=None, consts=None, mem_bytes=32 << 30, max_schedules=1 << 36, metrics=False, device=0):
+    """The notebook's run_brute_force_kalman_filter on the GPU: every schedule of one pick per
+    sampling window (schedule_queues) as its own filter, scored by the position RMSE of its
+    trajectory against ``track`` (track_positions; None = the event list's own fixes), the first
+    schedule in itertools.product order with the strictly smallest score kept.  Without a warm
+    start (initial_pt, initial_state = a driver's P and states[-1]) x0 = 0, P0 = SCHEDULE_P0 and
+    the first pick's dt is 0, as in the notebook.  The search runs as kf_search_schedules, with
+    the smallest number of fixed leading windows whose plan fits ``mem_bytes``, the classes one
+    after another and (metric, global rank) reduced here; the winner is then run through
+    kf_run_events for its trajectory.  Raises ValueError when the space exceeds ``max_schedules``
+    (the notebook warns and never finishes).  Returns a dict: the notebook's selected_sensors,
+    final_state, final_covariance, trajectory [(t, x, y, z, roll, pitch, yaw)], accuracy_metric
+    (None x 4 and inf with no complete window or no finite metric), and rank, digits, n_valid,
+    n_schedules, n_fixed, q_len, metrics (a device tensor of every metric in product order with
+    ``metrics``, else None)."""
+    queues = schedule_queues(events, start_idx, end_idx, frequency)
+    out = {'selected_sensors': None, 'final_state': None, 'final_covariance': None, 'trajectory': None,
+           'accuracy_metric': float('inf'), 'rank': None, 'digits': None, 'n_valid': 0, 'n_schedules': 0,
+           'n_fixed': 0, 'q_len': [len(q) for q in queues], 'metrics': None}
+    if not queues:
+        return out
+    log_n = sum(math.log10(len(q)) for q in queues)
+    if log_n > math.log10(max_schedules):
+        raise ValueError(f'the windows hold about 1e{log_n:.1f} schedules (log10 = {log_n:.2f}), more than '
+                         f'max_schedules = {max_schedules}; shorten the slice or lower the frequency')
+    q_len, ev, ref = schedule_arrays(queues, *_track_of(events, track))
+    W = len(queues)
+    n_total = math.prod(int(q) for q in q_len)
+    x0 = np.zeros(15)
+    if initial_pt is not None and initial_state is not None:
+        P = np.asarray(initial_pt, np.float64)
+        x0[0:6] = initial_state[1:7]
+        prev = float(initial_state[0])
+    else:
+        P, prev = SCHEDULE_P0, float('nan')
+    P0b = to_blocks(P)
+    init = np.concatenate([x0, P0b])
+    kf = BatchedKF('ref15', 1, 'f64', device=device, params=_params(consts))
+    try:
+        for n_fixed in range(W + 1):
+            plan = kf.schedule_plan(q_len, n_fixed)
+            if (plan['n_free'] is not None and plan['widest'] <= SCHEDULE_MAX_NODES
+                    and plan['workspace_bytes'] <= mem_bytes):
+                break
+        else:
+            raise ValueError(f'no split of the {W} windows fits mem_bytes = {mem_bytes}')
+        n_free = plan['n_free']
+        mt = torch.empty(n_total, dtype=torch.float64, device=kf.device) if metrics else None
+        best = (float('inf'), None, None)
+        n_valid = 0
+        for c, fixed in enumerate(itertools.product(*(range(int(q)) for q in q_len[:n_fixed]))):
+            sl = mt[c * n_free:(c + 1) * n_free] if mt is not None else False
+            rank, digits, metric, nv, _ = kf.search_schedules(ev, q_len, ref, init, prev, fixed=fixed, metrics=sl)
+            n_valid += nv
+            if rank is not None and metric < best[0]:  # classes in rank order: a tie keeps the earlier
+                best = (metric, c * n_free + rank, digits)
+        out.update(n_valid=n_valid, n_schedules=n_total, n_fixed=n_fixed, metrics=mt)
+        if best[1] is None:
+            return out
+        metric, rank, digits = best
+        picks = [queues[w][d] for w, d in enumerate(digits)]
+        stream, last = [], prev
+        for _, stype, t, sdata in picks:
+            stream.append((GPS if stype == 'GPS' else IMU, 0.0 if last != last else t - last,
+                           event_payload(stype, sdata)))
+            last = t
+        tr, _, _, x, Pb, _ = _run_streams([stream], x0[None], P0b[None], 'f64', device, consts=consts, kf=kf)
+    finally:
+        kf.close()
+    out.update(selected_sensors=tuple(picks), final_state=x[:, 0].copy(), final_covariance=from_blocks(Pb[:, 0]),
+               trajectory=[(p[2], *tr[i + 1, :, 0]) for i, p in enumerate(picks)], accuracy_metric=metric,
+               rank=rank, digits=digits)
+    return out
 
 
 # --------------------------------------------------------------------------------------------
