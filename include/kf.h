@@ -143,7 +143,10 @@ const char* kf_version(void);
  *                         4 = one gated f64 filter (B = 1, gate) with closed-form look-ahead
  *                         over runs of predict-only events (8 events per wave step: 2.3x
  *                         the chain kernel at 3 % updated, slower from about 20 %; the
- *                         gated stream fallback picks it by itself, see kf_run_stream)
+ *                         gated stream fallback picks it by itself, see kf_run_stream).
+ *                         With 1, kf_run_events never takes its one-filter route through
+ *                         kf_run_stream (the run stays on the lane kernel) and kf_run_stream
+ *                         itself is KF_EINVAL: its fallback cannot run on the lane kernel
  *   KF_OPT_STREAM         kf_run_events: 0 = route one long filter through kf_run_stream,
  *                         1 = never (every filter in sequence)
  *   KF_OPT_STREAM_CHUNKS  kf_run_stream: target chunk count (>= 2); 0 = 8192
@@ -375,7 +378,9 @@ int kf_run_events_gates(kf_batch* handle, int T, const uint8_t* etype, const dou
  * flags requested, a fallback whose chunked pass updated at most 1 event in 8 runs the
  * look-ahead kernel (KF_OPT_EVENTS_KERNEL = 4: same flags, records to rounding, 1.8e-12
  * relative measured), chosen on the device (KF_OPT_EVENTS_KERNEL = 2 keeps the chain
- * kernel).  The run of
+ * kernel, 4 the look-ahead kernel).  KF_OPT_EVENTS_KERNEL = 1 (the lane kernel, which cannot run
+ * the fallback) is KF_EINVAL here, before anything is queued; kf_run_events with it does not take
+ * this route.  The run of
  * run_kalman_filter_full (kf_workers.py:623-728) over a whole drive log. */
 int kf_run_stream(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
                   void* traj, void* cov, void* logdet, uint8_t* updated, int chunk, int warmup,
@@ -446,9 +451,10 @@ int kf_run_tails(kf_batch* handle, int T, const uint8_t* etype, const double* dt
  * the map pass: NaN = not measured, the chunk starts being the composed maps' values, or inf for
  * a non-finite chunk start), out[4] = chunks (1: the stream was too short to split
  * and ran sequentially), out[5] = chunk length, out[6] = events of event warm-up, out[7] = the
- * sequential fallback's kernel (0 = none, the chunked records stood; 2 = the chain kernel; 4 =
- * the look-ahead kernel, which a gated f64 run takes when its chunked pass updated at most 1
- * event in 8).  out: 8 doubles. */
+ * sequential fallback's kernel that ran (0 = none: the chunked records stood, or out[4] = 1 and
+ * there was nothing to fall back from; 2 = the chain kernel; 4 = the look-ahead kernel, which a
+ * gated f64 run takes when its chunked pass updated at most 1 event in 8, or always with
+ * KF_OPT_EVENTS_KERNEL = 4).  out: 8 doubles. */
 int kf_stream_check(kf_batch* handle, double* out, void* stream);
 
 /* KF_MODEL_REF15 brute-force search: filter f of the handle evaluates combination number

@@ -44,6 +44,10 @@ struct kf_batch {
     void* stream_ws;  // kf_run_stream: chunk banks, maps, check (grown on demand)
     size_t stream_ws_bytes;
     int64_t s_chunks, s_len, s_warm;  // the last kf_run_stream's split (s_chunks = 1: sequential)
+    // the sequential fallback the last kf_run_stream queued behind its checks: kStreamFallbackNone
+    // (s_chunks = 1: nothing was split), a kfmi::kEvents* variant, or kStreamFallbackDevice (the
+    // look-ahead and the chain kernel both queued, the device's StreamCheck flags pick one)
+    int s_fallback;
     // BASELINE models: a kf_predict held back so the next kf_update runs predict + update as one
     // fused step (the state crosses HBM once instead of twice).  The control is copied into
     // pend_u on the predict's stream, so the caller may reuse its u buffer at once.
@@ -863,24 +867,9 @@ int kf_synth(kf_batch* h, uint64_t seed, int64_t filter_offset, int T, double dt
 
 namespace {
 
-// kf_run_events' kernel choice and launch (skip: device flag, see RefArgs::skip; variant >= 0:
-// that kernel, for the stream fallback's device-side choice)
-int run_events_launch(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, void* traj,
-                      void* cov, void* logdet, uint8_t* updated, int gate, double threshold, const int32_t* skip,
-                      void* stream, int forced = -1, const double* thresholds = nullptr) {
-    kfmi::RefArgs a = ref_args(h);
-    a.thresholds = thresholds;  // kf_run_events_gates: per-filter gates (gate / threshold unused)
-    a.T = T;
-    a.etype = etype;
-    a.dt = dt;
-    a.payload = payload;
-    a.traj = traj;
-    a.cov = cov;
-    a.logdet = logdet;
-    a.updated = updated;
-    a.gate = gate;
-    a.threshold = threshold;
-    a.skip = skip;
+// the kernel (kfmi::kEvents*) a run of the handle's filters takes, by its size and
+// KF_OPT_EVENTS_KERNEL; gate: the run has one scalar gate
+int events_variant(const kf_batch* h, int gate) {
     // Few filters cannot fill the chip one lane each: give every axis chain its own lane
     // (8 lanes per filter).  Otherwise one lane per filter, with the inputs staged through LDS
     // by DMA where its layout conditions hold.  KF_OPT_EVENTS_KERNEL = 1 | 2 | 3 (lane, chain,
@@ -900,7 +889,28 @@ int run_events_launch(kf_batch* h, int T, const uint8_t* etype, const double* dt
     else if (v == 1) variant = kfmi::kEventsLane;
     else if (v == 3 && lds_ok) variant = kfmi::kEventsLds;
     else if (v == 4 && h->B == 1 && gate && h->dtype == KF_F64) variant = kfmi::kEventsGated;
-    if (forced >= 0) variant = forced;
+    return variant;
+}
+
+// kf_run_events' kernel choice and launch (skip: device flag, see RefArgs::skip; forced >= 0:
+// that kernel, for the stream fallback's device-side choice)
+int run_events_launch(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, void* traj,
+                      void* cov, void* logdet, uint8_t* updated, int gate, double threshold, const int32_t* skip,
+                      void* stream, int forced = -1, const double* thresholds = nullptr) {
+    kfmi::RefArgs a = ref_args(h);
+    a.thresholds = thresholds;  // kf_run_events_gates: per-filter gates (gate / threshold unused)
+    a.T = T;
+    a.etype = etype;
+    a.dt = dt;
+    a.payload = payload;
+    a.traj = traj;
+    a.cov = cov;
+    a.logdet = logdet;
+    a.updated = updated;
+    a.gate = gate;
+    a.threshold = threshold;
+    a.skip = skip;
+    const int variant = forced >= 0 ? forced : events_variant(h, gate);
     if (skip && variant != kfmi::kEventsChain && variant != kfmi::kEventsGated)
         return fail(KF_EINVAL, "kf_run_stream: fallback needs the chain kernel");
     hipError_t e = kfmi::launch_ref_events(h->model, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream), variant);
@@ -917,6 +927,8 @@ constexpr int kStreamGateWarmup = 2048;
 // the chunked pass (70,000 events: 1.4x the chain kernel at 11 %, 0.74x at 22 %;
 // profiles/r06_lookahead/ab_f64.log)
 constexpr int kStreamLookaheadShare = 8;
+// kf_batch::s_fallback beside the kfmi::kEvents* variants
+constexpr int kStreamFallbackNone = -1, kStreamFallbackDevice = -2;
 // default (warmup < 0): covariance maps iterated to cover this many events, then kStreamPolish
 // chunks of event warm-up
 constexpr int64_t kStreamLftEvents = 2048;
@@ -969,8 +981,9 @@ int kf_run_events(kf_batch* h, int T, const uint8_t* etype, const double* dt, co
     if (!check_events_args(h, T, etype, dt, payload, "kf_run_events", &rc)) return rc;
     // one filter over a long stream: parallel over time (checked, with a sequential fallback);
     // gated (the adaptive threshold) from an event warm-up; KF_OPT_STREAM = 1 turns the route
-    // off for the handle, kf_run_events_seq for one call
-    if (h->B == 1 && T >= kStreamMinEvents && opt(h, KF_OPT_STREAM) == 0)
+    // off for the handle, kf_run_events_seq for one call.  KF_OPT_EVENTS_KERNEL = 1 (lane) stays
+    // on the kernel the caller asked for: the route's fallback cannot run on it
+    if (h->B == 1 && T >= kStreamMinEvents && opt(h, KF_OPT_STREAM) == 0 && opt(h, KF_OPT_EVENTS_KERNEL) != 1)
         return run_stream_impl(h, T, etype, dt, payload, traj, cov, logdet, updated, 0, gate ? kStreamGateWarmup : -1,
                                gate, threshold, stream);
     return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold, nullptr, stream);
@@ -1129,6 +1142,11 @@ int run_stream_impl(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
     if (!is_ref(h)) return fail(KF_EINVAL, "kf_run_stream: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle");
     if (h->B != 1) return fail(KF_EINVAL, "kf_run_stream: needs a handle of one filter (B = %lld)", (long long)h->B);
     if (T < 0) return fail(KF_EINVAL, "kf_run_stream: T = %d < 0", T);
+    // checked before anything is queued: the sequential fallback skips on a device flag, which
+    // the lane kernel does not read
+    if (opt(h, KF_OPT_EVENTS_KERNEL) == 1)
+        return fail(KF_EINVAL, "kf_run_stream: KF_OPT_EVENTS_KERNEL = 1 (lane) cannot run the sequential fallback; "
+                               "use 0, 2 or 4, or kf_run_events_seq");
     if (T == 0) return KF_OK;
     if (!etype || !dt || !payload) return fail(KF_EINVAL, "kf_run_stream: null etype/dt/payload stream");
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1151,6 +1169,7 @@ int run_stream_impl(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
     h->s_warm = W;
     if (C < 2 || !fits || L > INT32_MAX || W > INT32_MAX) {
         h->s_chunks = 1;
+        h->s_fallback = kStreamFallbackNone;
         return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold, nullptr,
                                  stream);
     }
@@ -1322,6 +1341,7 @@ int run_stream_impl(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
     // kernel (2.3x the chain kernel at 3 % updated, slower from about 20 %), chosen
     // on the device: both launches are queued and each returns on its flag
     if (gate && f64 && updated && opt(h, KF_OPT_EVENTS_KERNEL) == 0) {
+        h->s_fallback = kStreamFallbackDevice;
         e = kfmi::launch_stream_choose(sa.check, updated, T, kStreamLookaheadShare, st);
         if (e != hipSuccess) return hip_fail(e, "kf_run_stream");
         int rc = run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold,
@@ -1330,8 +1350,9 @@ int run_stream_impl(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
         return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold,
                                  &sa.check->skip_chain, stream, kfmi::kEventsChain);
     }
+    h->s_fallback = events_variant(h, gate);
     return run_events_launch(h, T, etype, dt, payload, traj, cov, logdet, updated, gate, threshold, &sa.check->ok,
-                             stream);
+                             stream, h->s_fallback);
 }
 }  // namespace
 
@@ -1352,8 +1373,12 @@ int kf_stream_check(kf_batch* h, double* out, void* stream) {
     out[4] = double(h->s_chunks);
     out[5] = double(h->s_len);
     out[6] = double(h->s_warm);
-    // the sequential fallback's kernel: 0 none (the chunked records stood), 2 chain, 4 look-ahead
-    out[7] = h->s_chunks > 1 && k.ok ? 0.0 : k.skip_chain ? 4.0 : 2.0;
+    // the sequential fallback's kernel: 0 none (the chunked records stood, or nothing was split
+    // and no fallback was queued), 2 chain, 4 look-ahead.  What the host queued decides; the
+    // device's flags are read only where it queued both and the device chose
+    int fb = h->s_chunks > 1 && !k.ok ? h->s_fallback : kStreamFallbackNone;
+    if (fb == kStreamFallbackDevice) fb = k.skip_chain ? kfmi::kEventsGated : kfmi::kEventsChain;
+    out[7] = fb == kfmi::kEventsGated ? 4.0 : fb == kfmi::kEventsChain ? 2.0 : 0.0;
     return KF_OK;
 }
 
