@@ -768,11 +768,164 @@ struct ChainIn {
     T va, vb;
 };
 
+// One lane of the 8-lanes-per-filter kernels (ref_chain_kernel, ref_sweep_kernel,
+// ref_chain_gated_kernel): which chain lane c of a group runs, where that chain's states, block
+// rows and payload columns are, its noise constants, and the event all three kernels run.  The
+// kernels keep their own address tables (state banks, record rows, stream columns).
+template <typename T, class M, bool CUSTOM>
+struct ChainLane {
+    int c;       // lane of the group
+    bool pva;    // a (pos, vel, acc) chain; otherwise an (att, rate) chain or none
+    bool live;   // the lane holds a chain
+    int ca;      // the chain's axis among its kind
+    int xi[3];   // state indices (-1: none)
+    int pr[6];   // block-packed covariance rows (-1: none)
+    int ia, ib;  // payload columns: GPS position / IMU attitude, IMU acceleration / rate
+    T q[3], Rimu[6], Rgps;
+
+    __device__ __forceinline__ ChainLane(int lane, const RefConsts* kc)
+        : c(lane), pva(lane < M::NP), live(lane < M::NP + M::NA), ca(pva ? lane : (live ? lane - M::NP : 0)) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;  // (tt tw ww) of the 3x3 packing
+            pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
+        }
+        ia = pva ? ca : M::imu_att(ca);
+        ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);
+        q[0] = T(pva ? kQPos : kQAtt), q[1] = T(pva ? kQVel : kQRate), q[2] = T(pva ? kQAcc : 0.0);
+        Rimu[0] = T(pva ? kRPos : kRAtt), Rimu[3] = T(pva ? kRVel : kRRate), Rimu[5] = T(pva ? kRAcc : 1.0);
+        Rimu[1] = Rimu[2] = Rimu[4] = T(0);
+        Rgps = T(kRGps);
+        if constexpr (CUSTOM) {  // this lane's chain states (the inert third state of an aw lane keeps 0 / 1)
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (xi[k] >= 0) {
+                    q[k] = T(ro(kc)->q[xi[k]]);
+                    Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
+                }
+            if (pva) Rgps = T(ro(kc)->r_gps[ca]);
+        }
+    }
+
+    // P[k] where the lane holds no row k: the identity (an aw lane's inert state has variance 1)
+    static __device__ __forceinline__ T unit(int k) { return T(k == 0 || k == 3 || k == 5 ? 1 : 0); }
+
+    // One event on this lane's chain, for NL states that share the covariance: predict, the
+    // adaptive gate (gated: against thr, through the group's GateBand), the GPS / IMU update,
+    // the aw lane's inert-state reset, and NaN poisoning of the whole group when any of its chains
+    // failed (st then kNotSpd).  Returns whether the update was applied; every lane of the group
+    // must call it together (the gate and the poisoning exchange over the group).
+    template <int NL>
+    __device__ __forceinline__ bool event(int type, T dt, T va, T vb, bool gated, const GateBand<T>& gate, T thr,
+                                          T (&x)[NL][3], T (&P)[6], int32_t& st) const {
+        if (type == 255) return false;
+        // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
+        const T c02 = pva ? T(0.5) * dt * dt : T(0);
+        const T c12 = pva ? dt : T(0);
+#pragma unroll
+        for (int v = 0; v < NL; ++v) {
+            const T xn0 = fmaT(c02, x[v][2], fmaT(dt, x[v][1], x[v][0]));
+            const T xn1 = fmaT(c12, x[v][2], x[v][1]);
+            x[v][0] = xn0;
+            x[v][1] = xn1;
+        }
+        T FP[3][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
+            FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
+            FP[2][j] = P[tri<3>(2, j)];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                T s = FP[i][j];
+                if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
+                if (j == 1) s = fmaT(FP[i][2], c12, s);
+                P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
+            }
+        bool applied = (type == kGps || type == kImu);
+        if (gated && applied) applied = gate.open(P, live, thr);
+        bool ok = true;
+        if (applied) {
+            if (type == kGps) {
+                if (pva) {
+                    T zb[NL][1];
+#pragma unroll
+                    for (int v = 0; v < NL; ++v) zb[v][0] = va;
+                    const T R[1] = {Rgps};
+                    ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
+                }
+            } else {
+                T zb[NL][3];
+#pragma unroll
+                for (int v = 0; v < NL; ++v) {
+                    const T V = fmaT(vb, dt, x[v][1]);
+                    const T X = fmaT(V, dt, x[v][0]);
+                    zb[v][0] = pva ? X : va;
+                    zb[v][1] = pva ? V : vb;
+                    zb[v][2] = pva ? vb : T(0);
+                }
+                ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
+                if (!pva) {  // reset the inert state
+#pragma unroll
+                    for (int v = 0; v < NL; ++v) x[v][2] = T(0);
+                    P[5] = T(1);
+                }
+            }
+        }
+        if (group_any(!ok)) {
+            st = kNotSpd;
+#pragma unroll
+            for (int v = 0; v < NL; ++v)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) x[v][k] = quiet_nan<T>();
+#pragma unroll
+            for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
+        }
+        return applied;
+    }
+};
+
+// The input ring of the chain-layout kernels: event t's inputs are loaded D - 1 events ahead
+// through a fully unrolled ring of named buffers (static indices, no loop-carried copies).
+// load(t, in) is called for t up to n + D - 2 and clamps past-the-end events itself (they re-read
+// a last event); the prologue's loads are drained once, so no in-loop wait targets them (vmcnt
+// counts in order: the step's wait for its own buffer then leaves the D - 1 younger loads in
+// flight).  Each depth adds a copy of the event body (48 KB of code at 8).  Depths 2, 3, 4 and 8
+// were A/B-measured on config 1 (one filter, per-filter layout) without a resolvable difference: a
+// single wave's launch time varies +-10% from launch to launch
+// (profiles/r01_ab/chain_depth_inproc.json), so that default stays at 2.  Stream mode gathers
+// each filter's events from its own part of the stream (a cache line per 1.8 events, lines differ
+// per filter), so its loads see HBM latency: a deeper ring.
+template <int D, typename T, class Load, class Step>
+__device__ __forceinline__ void ring_run(int n, Load&& load, Step&& step) {
+    if (n <= 0) return;
+    ChainIn<T> buf[D];
+#pragma unroll
+    for (int j = 0; j < D - 1; ++j) load(j, buf[j]);
+    __builtin_amdgcn_s_waitcnt(0);
+    int t = 0;
+    for (; t + D <= n; t += D) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            load(t + j + D - 1, buf[(j + D - 1) % D]);
+            step(t + j, buf[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < D - 1; ++j)
+        if (t + j < n) step(t + j, buf[j]);
+}
+
 // NV > 1 (stream mode only): NV variants of each filter that differ only in their start state
 // (kf_run_stream's map pass: a chunk from its guess and from the guess + delta on each chain
 // component) share one lane.  The covariance recursion does not read the state, so P, S and K
-// are computed once per event and every variant's state is updated with them (sel_update_nv);
-// each variant's arithmetic is the single-state lane's, term for term.  Variant v's state is
+// are computed once per event and every variant's state is updated with them (ChainLane::event's
+// NL states through sel_update_nv).  Variant v's state is
 // column v * B + f of a state bank of NV * B columns (the covariance: column f), and its
 // trajectory records go to rows v * s_vstride.
 // GATES (kf_run_events_gates, per-filter layout): each 8-lane group gates its filter by its own
@@ -787,25 +940,18 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     const int64_t f = g / LPF;
     if (f >= a.B) return;  // whole groups leave together (LPF divides the wave)
-    const int c = static_cast<int>(g % kGroup);
+    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), a.kc);
+    const int c = L.c;
+    const bool pva = L.pva, live = L.live;
+    const auto& xi = L.xi;
+    const auto& pr = L.pr;
     const int vb = NL < NV ? int((g % LPF) / kGroup) * NL : 0;  // this lane's first variant
-    const bool pva = c < M::NP;
-    const bool live = c < M::NP + M::NA;
-    const int ca = pva ? c : (live ? c - M::NP : 0);
     const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
     const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
     const uint32_t rbank = uint32_t(NV) * rb;  // row stride of the state / covariance bank
     const uint32_t rb8 = uint32_t(a.B) * 8u;
     const uint32_t off8 = uint32_t(f) * 8u;
-    // this lane's state indices and block rows (-1: none), as voffsets into row spans
-    int xi[3], pr[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;  // (tt tw ww) of the 3x3 packing
-        pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
-    }
+    // this lane's state and block rows as voffsets into row spans
     uint32_t vx[3], vp[6];
 #pragma unroll
     for (int k = 0; k < 3; ++k) vx[k] = xi[k] >= 0 ? uint32_t(xi[k]) * rbank + off : kDropOffset;
@@ -813,22 +959,7 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
     for (int k = 0; k < 6; ++k) vp[k] = pr[k] >= 0 ? uint32_t(pr[k]) * rbank + off : kDropOffset;
     const uint32_t v_tr = (xi[0] >= 0 && xi[0] < M::NTRAJ) ? uint32_t(xi[0]) * rb + off : kDropOffset;
     const uint32_t v_ld = c == 0 ? off : kDropOffset;
-    const int ia = pva ? ca : M::imu_att(ca);              // GPS position / IMU attitude column
-    const int ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);  // IMU acceleration / rate column
-    const uint32_t v_a = uint32_t(ia) * rb + off, v_b = uint32_t(ib) * rb + off;
-    T q[3] = {T(pva ? kQPos : kQAtt), T(pva ? kQVel : kQRate), T(pva ? kQAcc : 0.0)};
-    T Rimu[6] = {T(pva ? kRPos : kRAtt), T(0), T(0), T(pva ? kRVel : kRRate), T(0), T(pva ? kRAcc : 1.0)};
-    T Rgps = T(kRGps);
-    if constexpr (CUSTOM) {  // this lane's chain states (the inert third state of an aw lane keeps 0 / 1)
-        const RefConsts* kc = a.kc;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (xi[k] >= 0) {
-                q[k] = T(ro(kc)->q[xi[k]]);
-                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
-            }
-        if (pva) Rgps = T(ro(kc)->r_gps[ca]);
-    }
+    const uint32_t v_a = uint32_t(L.ia) * rb + off, v_b = uint32_t(L.ib) * rb + off;
 
     T x[NL][3], P[6];
     T xs0[3];  // variant 0's start (the map pass's guess)
@@ -840,7 +971,7 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
             for (int k = 0; k < 3; ++k)
                 x[v][k] = ldv(rx, vx[k] == kDropOffset ? kDropOffset : vx[k] + uint32_t(vb + v) * rb, T(0));
 #pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
         if constexpr (NL < NV) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) xs0[k] = ldv(rx, vx[k], T(0));
@@ -862,14 +993,10 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
     }
     int32_t st = a.status[f];
     const bool need_ld = a.logdet != nullptr;
+    FilterGate<T> fg{a.gate != 0, T(a.threshold)};  // the launch's gate, or GATES: the filter's own
+    if constexpr (GATES) fg = gate_of<T>(a.thresholds, f);
     GateBand<T> gate;
-    FilterGate<T> fg{false, T(0)};
-    if constexpr (GATES) {
-        fg = gate_of<T>(a.thresholds, f);
-        if (fg.on) gate.init(a.thresholds[f]);
-    } else {
-        if (a.gate) gate.init(a.threshold);
-    }
+    if (fg.on) gate.init(GATES ? a.thresholds[f] : a.threshold);
     constexpr bool kLdBatch = STREAM && NV == 4 && kStreamLdBatch;
     T bm = T(1);  // kLdBatch: the group's determinant product of event (t - t mod 8 + c)
     int bex = 0;
@@ -911,8 +1038,8 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
             const int ty = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue, 0, 0));
             in.type = ue < S ? ty : 255;
             in.dt = ldv(r_dt, ue * 8u, 0.0);
-            in.va = ldv(r_pay, (ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T)), T(0));
-            in.vb = ldv(r_pay, (ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T)), T(0));
+            in.va = ldv(r_pay, (ue * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T)), T(0));
+            in.vb = ldv(r_pay, (ue * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T)), T(0));
         } else {
             in.type = int(ldb<uint8_t>(a.etype, t, uint32_t(a.B), uint32_t(f)));
             in.dt = ldb<double>(a.dt, t, rb8, off8);
@@ -922,81 +1049,7 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
         }
     };
     auto step = [&](int t, const ChainIn<T>& in) {
-        const int type = in.type;
-        const T dt = T(in.dt);
-        const T va = in.va, vb = in.vb;
-        bool applied = false;
-        if (type != 255) {
-            // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
-            const T c02 = pva ? T(0.5) * dt * dt : T(0);
-            const T c12 = pva ? dt : T(0);
-#pragma unroll
-            for (int v = 0; v < NL; ++v) {
-                const T xn0 = fmaT(c02, x[v][2], fmaT(dt, x[v][1], x[v][0]));
-                const T xn1 = fmaT(c12, x[v][2], x[v][1]);
-                x[v][0] = xn0;
-                x[v][1] = xn1;
-            }
-            T FP[3][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
-                FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
-                FP[2][j] = P[tri<3>(2, j)];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = i; j < 3; ++j) {
-                    T s = FP[i][j];
-                    if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
-                    if (j == 1) s = fmaT(FP[i][2], c12, s);
-                    P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
-                }
-            applied = (type == kGps || type == kImu);
-            if constexpr (GATES) {
-                if (fg.on && applied) applied = gate.open(P, live, fg.thr);
-            } else {
-                if (a.gate && applied) applied = gate.open(P, live, T(a.threshold));
-            }
-            bool ok = true;
-            if (applied) {
-                if (type == kGps) {
-                    if (pva) {
-                        T zb[NL][1];
-#pragma unroll
-                        for (int v = 0; v < NL; ++v) zb[v][0] = va;
-                        const T R[1] = {Rgps};
-                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
-                    }
-                } else {
-                    T zb[NL][3];
-#pragma unroll
-                    for (int v = 0; v < NL; ++v) {
-                        const T V = fmaT(vb, dt, x[v][1]);
-                        const T X = fmaT(V, dt, x[v][0]);
-                        zb[v][0] = pva ? X : va;
-                        zb[v][1] = pva ? V : vb;
-                        zb[v][2] = pva ? vb : T(0);
-                    }
-                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
-                    if (!pva) {  // reset the inert state
-#pragma unroll
-                        for (int v = 0; v < NL; ++v) x[v][2] = T(0);
-                        P[5] = T(1);
-                    }
-                }
-            }
-            if (group_any(!ok)) {
-                st = kNotSpd;
-#pragma unroll
-                for (int v = 0; v < NL; ++v)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) x[v][k] = quiet_nan<T>();
-#pragma unroll
-                for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
-            }
-        }
+        const bool applied = L.event(in.type, T(in.dt), in.va, in.vb, fg.on, gate, fg.thr, x, P, st);
         if constexpr (STREAM) {
             const uint32_t ue = uint32_t(e0 + t);
 #pragma unroll
@@ -1053,35 +1106,9 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
         }
     };
 
-    // Inputs are prefetched kChainDepth - 1 events ahead through a fully unrolled ring of named
-    // buffers (static indices, no loop-carried copies); loads past the end re-read the last
-    // event, and the prologue's loads are drained once so no in-loop wait targets them.  Depths
-    // 2, 3, 4 and 8 were A/B-measured on config 1 (one filter) without a resolvable difference:
-    // a single wave's launch time varies +-10% from launch to launch
-    // (profiles/r01_ab/chain_depth_inproc.json), and each depth adds a copy of the event body
-    // (48 KB of code at 8), so the default stays at 2.
-    // stream mode gathers each filter's events from its own part of the stream (a cache line
-    // per 1.8 events, lines differ per filter), so its loads see HBM latency: a deeper ring
     constexpr int D = STREAM ? (NV > 1 ? kStreamVarDepth : kStreamDepth) : kChainDepth;
     const int T_ = a.T;
-    auto load_c = [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); };
-    if (T_ > 0) {
-        ChainIn<T> buf[D];
-#pragma unroll
-        for (int j = 0; j < D - 1; ++j) load_c(j, buf[j]);
-        __builtin_amdgcn_s_waitcnt(0);
-        int t = 0;
-        for (; t + D <= T_; t += D) {
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                load_c(t + j + D - 1, buf[(j + D - 1) % D]);
-                step(t + j, buf[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < D - 1; ++j)
-            if (t + j < T_) step(t + j, buf[j]);
-    }
+    ring_run<D, T>(T_, [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); }, step);
     {
         const auto rx = span_rsrc(a.x, 0, rbank, M::N), rp = span_rsrc(a.P, 0, rbank, M::NBLK);
 #pragma unroll
@@ -1183,11 +1210,9 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 // :2298-2317) and their start state.  The chain kernel's layout, 8 lanes per filter and lane c on
 // axis chain c, so a wave carries 8 thresholds; every group reads the same stream entries (byte
 // range descriptors as in stream mode: the 8 groups' loads hit one cache line), and the event's
-// type and dt are wave-uniform.  Each event is the chain kernel's, term for term: predict,
-// GateBand::open against the group's own threshold, sel_update_nv, the aw lane's inert-state
-// reset, NaN poisoning per group.  The groups of a wave disagree about `applied`, so the wave
-// pays the update whenever one of its groups applies it: a sweep costs about what its
-// most-updating threshold costs.  Records in kf_run_events' layouts ([T][W][B], [T][B]), an
+// type and dt are wave-uniform.  Each event is ChainLane::event, gated by the group's own
+// threshold.  The groups of a wave disagree about `applied`, so the wave pays the update whenever
+// one of its groups applies it: a sweep costs about what its most-updating threshold costs.  Records in kf_run_events' layouts ([T][W][B], [T][B]), an
 // update count per filter, and the handle-layout state every ckpt_every events.
 //
 // TAILS (kf_run_tails): the same groups as ragged tails of the one stream.  Group f gathers its
@@ -1197,7 +1222,6 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 // branches diverge between groups (a group is active or inactive as a whole: its DPP reductions
 // stay legal).  The wave runs to its longest tail with the finished groups predicated off, and
 // the input ring clamps per group to the tail's own last event; an empty tail loads nothing.
-// Every other instantiation compiles to the code it was.
 // ------------------------------------------------------------------------------------
 #ifndef KF_SWEEP_DEPTH
 #define KF_SWEEP_DEPTH 4
@@ -1224,20 +1248,13 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
         wave_len = wave_uniform(wave_len);
     }
     if (f >= a.B) return;  // whole groups leave together
-    const int c = static_cast<int>(g % kGroup);
-    const bool pva = c < M::NP;
-    const bool live = c < M::NP + M::NA;
-    const int ca = pva ? c : (live ? c - M::NP : 0);
+    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), a.kc);
+    const int c = L.c;
+    const bool live = L.live;
+    const auto& xi = L.xi;
+    const auto& pr = L.pr;
     const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
     const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
-    int xi[3], pr[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;  // (tt tw ww) of the 3x3 packing
-        pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
-    }
     uint32_t vx[3], vp[6];
 #pragma unroll
     for (int k = 0; k < 3; ++k) vx[k] = xi[k] >= 0 ? uint32_t(xi[k]) * rb + off : kDropOffset;
@@ -1246,21 +1263,6 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     const uint32_t v_tr = (xi[0] >= 0 && xi[0] < M::NTRAJ) ? uint32_t(xi[0]) * rb + off : kDropOffset;
     const uint32_t v_ld = c == 0 ? off : kDropOffset;
     const uint32_t v_up = c == 0 ? uint32_t(f) : kDropOffset;
-    const int ia = pva ? ca : M::imu_att(ca);              // GPS position / IMU attitude column
-    const int ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);  // IMU acceleration / rate column
-    T q[3] = {T(pva ? kQPos : kQAtt), T(pva ? kQVel : kQRate), T(pva ? kQAcc : 0.0)};
-    T Rimu[6] = {T(pva ? kRPos : kRAtt), T(0), T(0), T(pva ? kRVel : kRRate), T(0), T(pva ? kRAcc : 1.0)};
-    T Rgps = T(kRGps);
-    if constexpr (CUSTOM) {  // this lane's chain states (the inert third state of an aw lane keeps 0 / 1)
-        const RefConsts* kc = a.kc;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (xi[k] >= 0) {
-                q[k] = T(ro(kc)->q[xi[k]]);
-                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
-            }
-        if (pva) Rgps = T(ro(kc)->r_gps[ca]);
-    }
 
     T x[1][3], P[6];
     if constexpr (TAILS) {
@@ -1275,13 +1277,13 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[0][k] = xi[k] >= 0 ? sx[int64_t(xi[k]) * sb] : T(0);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? sp[int64_t(pr[k]) * sb] : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? sp[int64_t(pr[k]) * sb] : L.unit(k);
     } else {
         const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[0][k] = ldv(rx, vx[k], T(0));
 #pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
     }
     // a tail from a source column starts with status OK, as after kf_set_state
     int32_t st = (TAILS && tl.src_row >= 0) ? 0 : a.status[f];
@@ -1300,80 +1302,20 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     const uint32_t S = uint32_t(a.T);
     const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
     const auto r_pay = bytes_rsrc(a.payload, S * 9u * uint32_t(sizeof(T)));
-    auto load = [&](int t, ChainIn<T>& in) {
-        const uint32_t ue = uint32_t(t);
-        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue, 0, 0));
-        in.dt = ldv(r_dt, ue * 8u, 0.0);
-        in.va = ldv(r_pay, (ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T)), T(0));
-        in.vb = ldv(r_pay, (ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T)), T(0));
+    // stream event ue's inputs; dead = ~0u drops the loads (offset 2^32 - 1 lies past every byte
+    // range, the 4 GiB payload's too)
+    auto load = [&](uint32_t ue, uint32_t dead, ChainIn<T>& in) {
+        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue | dead, 0, 0));
+        in.dt = ldv(r_dt, (ue * 8u) | dead, 0.0);
+        in.va = ldv(r_pay, ((ue * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T))) | dead, T(0));
+        in.vb = ldv(r_pay, ((ue * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T))) | dead, T(0));
     };
     int ck_left = TAILS ? 0 : a.ckpt_every;  // events until the next checkpoint (wave-uniform)
     int ck_row = 0;
     auto step = [&](int t, const ChainIn<T>& in) {
         // every lane of the wave loaded the same type and dt: scalars (TAILS: the group's own)
         const int type = TAILS ? in.type : wave_uniform(in.type);
-        const T dt = T(in.dt);
-        const T va = in.va, vb = in.vb;
-        bool applied = false;
-        if (type != 255) {
-            // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
-            const T c02 = pva ? T(0.5) * dt * dt : T(0);
-            const T c12 = pva ? dt : T(0);
-            {
-                const T xn0 = fmaT(c02, x[0][2], fmaT(dt, x[0][1], x[0][0]));
-                const T xn1 = fmaT(c12, x[0][2], x[0][1]);
-                x[0][0] = xn0;
-                x[0][1] = xn1;
-            }
-            T FP[3][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
-                FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
-                FP[2][j] = P[tri<3>(2, j)];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = i; j < 3; ++j) {
-                    T s = FP[i][j];
-                    if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
-                    if (j == 1) s = fmaT(FP[i][2], c12, s);
-                    P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
-                }
-            applied = (type == kGps || type == kImu);
-            if (applied && !always) applied = gate.open(P, live, thr);
-            bool ok = true;
-            if (applied) {
-                if (type == kGps) {
-                    if (pva) {
-                        T zb[1][1];
-                        zb[0][0] = va;
-                        const T R[1] = {Rgps};
-                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
-                    }
-                } else {
-                    T zb[1][3];
-                    const T V = fmaT(vb, dt, x[0][1]);
-                    const T X = fmaT(V, dt, x[0][0]);
-                    zb[0][0] = pva ? X : va;
-                    zb[0][1] = pva ? V : vb;
-                    zb[0][2] = pva ? vb : T(0);
-                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
-                    if (!pva) {  // reset the inert state
-                        x[0][2] = T(0);
-                        P[5] = T(1);
-                    }
-                }
-            }
-            if (group_any(!ok)) {
-                st = kNotSpd;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) x[0][k] = quiet_nan<T>();
-#pragma unroll
-                for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
-            }
-        }
+        const bool applied = L.event(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st);
         nup += applied ? 1 : 0;
         // absent records: skipped by wave-uniform branches
         if (need_tr) stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, x[0][0]);
@@ -1397,62 +1339,19 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
         }
     };
 
-    // the chain kernel's input ring (kSweepDepth - 1 events ahead; loads past the end re-read
-    // the last event)
-    constexpr int D = kSweepDepth;
     if constexpr (TAILS) {
-        // the same ring over the wave's longest tail: step s is the group's event lo + s, loaded
-        // through the stream's descriptors at that offset and clamped to the tail's own last event
-        // (so never past T - 1); a group past its tail is predicated off, and an empty tail's
-        // loads are dropped (offset 2^32 - 1 lies past every byte range, the 4 GiB payload's too)
+        // the ring over the wave's longest tail (finite, wave-uniform, known before the loop): step s
+        // is the group's event lo + s, its loads clamped to the tail's own last event (so never past
+        // T - 1); a group past its tail is predicated off, and an empty tail loads nothing
         const uint32_t dead = len > 0 ? 0u : ~0u;
-        auto load_t = [&](int s, ChainIn<T>& in) {
-            const uint32_t ue = uint32_t(tl.lo + (s < len ? s : len - 1));
-            in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue | dead, 0, 0));
-            in.dt = ldv(r_dt, (ue * 8u) | dead, 0.0);
-            in.va = ldv(r_pay, ((ue * 9u + uint32_t(ia)) * uint32_t(sizeof(T))) | dead, T(0));
-            in.vb = ldv(r_pay, ((ue * 9u + uint32_t(ib)) * uint32_t(sizeof(T))) | dead, T(0));
-        };
-        auto step_t = [&](int s, const ChainIn<T>& in) {
-            if (s < len) step(s, in);
-        };
-        const int W_ = wave_len;  // finite, wave-uniform, known before the loop
-        if (W_ > 0) {
-            ChainIn<T> buf[D];
-#pragma unroll
-            for (int j = 0; j < D - 1; ++j) load_t(j, buf[j]);
-            __builtin_amdgcn_s_waitcnt(0);
-            int s = 0;
-            for (; s + D <= W_; s += D) {
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    load_t(s + j + D - 1, buf[(j + D - 1) % D]);
-                    step_t(s + j, buf[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < D - 1; ++j)
-                if (s + j < W_) step_t(s + j, buf[j]);
-        }
-    }
-    const int T_ = TAILS ? 0 : a.T;
-    auto load_c = [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); };
-    if (T_ > 0) {
-        ChainIn<T> buf[D];
-#pragma unroll
-        for (int j = 0; j < D - 1; ++j) load_c(j, buf[j]);
-        __builtin_amdgcn_s_waitcnt(0);
-        int t = 0;
-        for (; t + D <= T_; t += D) {
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                load_c(t + j + D - 1, buf[(j + D - 1) % D]);
-                step(t + j, buf[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < D - 1; ++j)
-            if (t + j < T_) step(t + j, buf[j]);
+        ring_run<kSweepDepth, T>(
+            wave_len, [&](int s, ChainIn<T>& in) { load(uint32_t(tl.lo + (s < len ? s : len - 1)), dead, in); },
+            [&](int s, const ChainIn<T>& in) {
+                if (s < len) step(s, in);
+            });
+    } else {
+        const int T_ = a.T;
+        ring_run<kSweepDepth, T>(T_, [&](int t, ChainIn<T>& in) { load(uint32_t(t < T_ ? t : T_ - 1), 0u, in); }, step);
     }
     {
         const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
@@ -1474,8 +1373,8 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
 // ------------------------------------------------------------------------------------
 // ONE gated filter (B = 1, the adaptive threshold, kf_workers.py:959-1058) whose gate blocks
 // most updates, on one wave: lane c + 8 j is chain c (the chain kernel's lane layout) of event
-// slot j.  Every event that applies an update runs as the chain kernel's event (its arithmetic,
-// term for term).  After an event that did not, the wave looks ahead over the next 8 events at
+// slot j.  Every event that applies an update runs as ChainLane::event, the same in every slot.
+// After an event that did not, the wave looks ahead over the next 8 events at
 // once: between two updates the filter only predicts, and with the model's additive F (F(a) F(b)
 // = F(a + b)) and diagonal Q(dt) a run of predicts has a closed form,
 //   P_m = F(tau_m) (P + S_m) F(tau_m)^T,  S_m = sum_{i <= m} F(-tau_i) Q(dt_i) F(-tau_i)^T,
@@ -1493,41 +1392,20 @@ template <typename T, class M, bool CUSTOM>
 __global__ __launch_bounds__(64) void ref_chain_gated_kernel(const RefArgs a) {
     if (a.skip && *a.skip) return;
     const int lane = int(threadIdx.x);
-    const int c = lane & (kGroup - 1);  // chain
-    const int slot = lane / kGroup;     // event slot of the look-ahead
-    const bool pva = c < M::NP;
-    const bool live = c < M::NP + M::NA;
-    const int ca = pva ? c : (live ? c - M::NP : 0);
-    int xi[3], pr[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;
-        pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
-    }
-    const int ia = pva ? ca : M::imu_att(ca);
-    const int ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);
-    T q[3] = {T(pva ? kQPos : kQAtt), T(pva ? kQVel : kQRate), T(pva ? kQAcc : 0.0)};
-    T Rimu[6] = {T(pva ? kRPos : kRAtt), T(0), T(0), T(pva ? kRVel : kRRate), T(0), T(pva ? kRAcc : 1.0)};
-    T Rgps = T(kRGps);
-    if constexpr (CUSTOM) {
-        const RefConsts* kc = a.kc;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (xi[k] >= 0) {
-                q[k] = T(ro(kc)->q[xi[k]]);
-                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
-            }
-        if (pva) Rgps = T(ro(kc)->r_gps[ca]);
-    }
+    const int slot = lane / kGroup;  // event slot of the look-ahead
+    const ChainLane<T, M, CUSTOM> L(lane & (kGroup - 1), a.kc);
+    const int c = L.c, ia = L.ia, ib = L.ib;
+    const bool pva = L.pva, live = L.live;
+    const auto& xi = L.xi;
+    const auto& pr = L.pr;
+    const auto& q = L.q;
     const T* hx = static_cast<const T*>(a.x);
     const T* hP = static_cast<const T*>(a.P);
     T x[1][3], P[6];
 #pragma unroll
     for (int k = 0; k < 3; ++k) x[0][k] = xi[k] >= 0 ? hx[xi[k]] : T(0);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? hP[pr[k]] : T(k == 0 || k == 3 || k == 5 ? 1 : 0);
+    for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? hP[pr[k]] : L.unit(k);
     int32_t st = a.status[0];
     GateBand<T> gate;
     gate.init(a.threshold);
@@ -1592,7 +1470,7 @@ __global__ __launch_bounds__(64) void ref_chain_gated_kernel(const RefArgs a) {
     double ndt = T_ > 0 ? a.dt[0] : 0.0;
     T nva = T_ > 0 ? pay[ia] : T(0), nvb = T_ > 0 ? pay[ib] : T(0);
     while (t < T_) {  // wave-uniform
-        // ---- event t as the chain kernel runs it (every slot the same arithmetic) ----
+        // ---- event t, every slot the same arithmetic ----
         if (nt != t) {
             ntype = int(a.etype[t]);
             ndt = a.dt[t];
@@ -1609,61 +1487,7 @@ __global__ __launch_bounds__(64) void ref_chain_gated_kernel(const RefArgs a) {
             nva = pay[int64_t(nt) * 9 + ia];
             nvb = pay[int64_t(nt) * 9 + ib];
         }
-        bool applied = false;
-        if (type != 255) {
-            const T c02 = pva ? T(0.5) * dt * dt : T(0);
-            const T c12 = pva ? dt : T(0);
-            {
-                const T xn0 = fmaT(c02, x[0][2], fmaT(dt, x[0][1], x[0][0]));
-                const T xn1 = fmaT(c12, x[0][2], x[0][1]);
-                x[0][0] = xn0;
-                x[0][1] = xn1;
-            }
-            T FP[3][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
-                FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
-                FP[2][j] = P[tri<3>(2, j)];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = i; j < 3; ++j) {
-                    T s = FP[i][j];
-                    if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
-                    if (j == 1) s = fmaT(FP[i][2], c12, s);
-                    P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
-                }
-            applied = (type == kGps || type == kImu);
-            if (applied) applied = gate.open(P, live, thr);
-            bool ok = true;
-            if (applied) {
-                if (type == kGps) {
-                    if (pva) {
-                        T zb[1][1] = {{va}};
-                        const T R[1] = {Rgps};
-                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
-                    }
-                } else {
-                    const T V = fmaT(vb, dt, x[0][1]);
-                    const T X = fmaT(V, dt, x[0][0]);
-                    T zb[1][3] = {{pva ? X : va, pva ? V : vb, pva ? vb : T(0)}};
-                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, 1, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
-                    if (!pva) {
-                        x[0][2] = T(0);
-                        P[5] = T(1);
-                    }
-                }
-            }
-            if (group_any(!ok)) {
-                st = kNotSpd;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) x[0][k] = quiet_nan<T>();
-#pragma unroll
-                for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
-            }
-        }
+        const bool applied = L.event(type, dt, va, vb, true, gate, thr, x, P, st);
         record_step(t, applied);
         ++t;
         // every lane holds the same decision (the gate's group ops, every slot the same event), but
@@ -2258,6 +2082,8 @@ __global__ __launch_bounds__(kBlock) void stream_records2_kernel(const StreamArg
 // reference's 200 Hz IMU stream contracts an error by ~1e-3), so a few iterations over all
 // chunks at once replace the W-event warm-up; the device seam check still decides.
 // ------------------------------------------------------------------------------------
+// ChainLane's noise table restated for the maps: fp64 whatever T is, R as reciprocals, and the
+// inert third state of an aw chain without a measurement (1 / R = 0) where the event has R = 1
 template <class M, bool CUSTOM>
 __device__ __forceinline__ void chain_noise(int ch, double (&q)[3], double (&si_imu)[3], double& si_gps,
                                             const RefConsts* kc) {
@@ -4808,6 +4634,30 @@ __global__ __launch_bounds__(kBlock) void schedule_finish_kernel(const uint64_t*
         }                                   \
     } while (0)
 
+// the statement with M = M15 / M8 and T = double / float in scope (model is 15 or 8: the
+// launchers check); KF_REF_DISPATCH adds CUSTOM
+#define KF_DTYPE_DISPATCH(f64, ...) \
+    do {                            \
+        if (f64) {                  \
+            using T = double;       \
+            __VA_ARGS__;            \
+        } else {                    \
+            using T = float;        \
+            __VA_ARGS__;            \
+        }                           \
+    } while (0)
+#define KF_MODEL_DISPATCH(model, f64, ...)          \
+    do {                                            \
+        if ((model) == 15) {                        \
+            using M = M15;                          \
+            KF_DTYPE_DISPATCH(f64, __VA_ARGS__);    \
+        } else {                                    \
+            using M = M8;                           \
+            KF_DTYPE_DISPATCH(f64, __VA_ARGS__);    \
+        }                                           \
+    } while (0)
+#define KF_REF_DISPATCH(model, f64, kc, ...) KF_CUSTOM_DISPATCH(kc, KF_MODEL_DISPATCH(model, f64, __VA_ARGS__))
+
 hipError_t launch_ref15_random_picks(const Ref15SchedArgs& a, int32_t* pick, hipStream_t stream) {
     if (a.B <= 0 || a.T < 0 || !a.words || !a.words_used || !a.n_sel || !a.sel_time || !pick) return hipErrorInvalidValue;
     ref15_random_picks_kernel<<<dim3(unsigned((a.B + kBlock - 1) / kBlock)), kBlock, 0, stream>>>(a, pick);
@@ -4963,60 +4813,28 @@ void ref_stream_t(const RefArgs& a, hipStream_t stream, int nv) {
 hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t stream, int variant) {
     if (model != 15 && model != 8) return hipErrorInvalidValue;
     if (a.thresholds && (variant == kEventsGated || a.s_len != 0)) return hipErrorInvalidValue;
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (model == 15) {
-            if (f64) ref_events_t<double, M15, CUSTOM>(a, stream, variant);
-            else ref_events_t<float, M15, CUSTOM>(a, stream, variant);
-        } else {
-            if (f64) ref_events_t<double, M8, CUSTOM>(a, stream, variant);
-            else ref_events_t<float, M8, CUSTOM>(a, stream, variant);
-        }
-    });
+    KF_REF_DISPATCH(model, f64, a.kc, ref_events_t<T, M, CUSTOM>(a, stream, variant));
     return hipGetLastError();
 }
 
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv) {
     if (a.s_len <= 0 || a.s_nchunks <= 0 || (nv != 1 && nv != 4)) return hipErrorInvalidValue;
     if (model != 15 && model != 8) return hipErrorInvalidValue;
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (model == 15) {
-            if (f64) ref_stream_t<double, M15, CUSTOM>(a, stream, nv);
-            else ref_stream_t<float, M15, CUSTOM>(a, stream, nv);
-        } else {
-            if (f64) ref_stream_t<double, M8, CUSTOM>(a, stream, nv);
-            else ref_stream_t<float, M8, CUSTOM>(a, stream, nv);
-        }
-    });
+    KF_REF_DISPATCH(model, f64, a.kc, ref_stream_t<T, M, CUSTOM>(a, stream, nv));
     return hipGetLastError();
 }
 
 hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
     if (a.B <= 0 || a.T < 0 || !a.tails || (model != 15 && model != 8)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (model == 15) {
-            if (f64) ref_sweep_kernel<double, M15, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
-            else ref_sweep_kernel<float, M15, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
-        } else {
-            if (f64) ref_sweep_kernel<double, M8, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
-            else ref_sweep_kernel<float, M8, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a);
-        }
-    });
+    KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a));
     return hipGetLastError();
 }
 
 hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
     if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (model == 15) {
-            if (f64) ref_sweep_kernel<double, M15, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
-            else ref_sweep_kernel<float, M15, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
-        } else {
-            if (f64) ref_sweep_kernel<double, M8, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
-            else ref_sweep_kernel<float, M8, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a);
-        }
-    });
+    KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
     return hipGetLastError();
 }
 
@@ -5081,15 +4899,8 @@ void stream_phase(int phase, const StreamArgs& a, hipStream_t stream) {
 
 hipError_t launch_stream_phase(int model, bool f64, int phase, const StreamArgs& a, hipStream_t stream) {
     if (a.C < 2 || phase < 0 || phase > kStreamPhaseRecords) return hipErrorInvalidValue;
-    if (model == 15) {
-        if (f64) stream_phase<double, M15>(phase, a, stream);
-        else stream_phase<float, M15>(phase, a, stream);
-    } else if (model == 8) {
-        if (f64) stream_phase<double, M8>(phase, a, stream);
-        else stream_phase<float, M8>(phase, a, stream);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    if (model != 15 && model != 8) return hipErrorInvalidValue;
+    KF_MODEL_DISPATCH(model, f64, stream_phase<T, M>(phase, a, stream));
     return hipGetLastError();
 }
 
@@ -5132,15 +4943,7 @@ hipError_t launch_stream_choose(StreamCheck* check, const uint8_t* updated, int6
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream) {
     const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
     if (model != 15 && model != 8) return hipErrorInvalidValue;
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (model == 15) {
-            if (f64) ref_reset_kernel<double, M15, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-            else ref_reset_kernel<float, M15, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        } else {
-            if (f64) ref_reset_kernel<double, M8, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-            else ref_reset_kernel<float, M8, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        }
-    });
+    KF_REF_DISPATCH(model, f64, a.kc, ref_reset_kernel<T, M, CUSTOM><<<grid, kBlock, 0, stream>>>(a));
     return hipGetLastError();
 }
 
