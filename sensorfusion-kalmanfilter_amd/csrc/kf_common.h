@@ -176,6 +176,16 @@ __device__ __forceinline__ T logdet_ldl(const T (&P)[N * (N + 1) / 2]) {
 // GAIN_R (H = I, M == N, diagonal R): P+ = K R.  I - K = (S - P) S^-1 = R S^-1, so
 // (I - K)P = R S^-1 P, the transpose of P S^-1 R = K R, and the product is symmetric: one multiply
 // per entry and no cancellation (P - K P subtracts nearly equal terms where P >> R).
+// Entry (i, j), i <= j, is taken as K[j][i] R[i], not K[i][j] R[j]: the two are equal only in exact
+// arithmetic.  After a gap of t seconds the chain's P is close to P_acc g g^T, g = (t^2/2, t, 1), and
+// row k of the gain equation K S = P has a right-hand side, and so an absolute error, proportional
+// to g_k: the row of the later state (velocity, acceleration) is the accurate one.  The position
+// row's cross terms fed the next fixes' velocity and acceleration gains (fp32 after a 20 s gap: 13
+// and 23 times the plain float32 NumPy filter's error; fp64 after 300 s: 3e-9 of the velocity scale).
+// JOSEPH = false with diagonal R and M < N (the fix): the observed rows take P+ H^T = K R as well
+// (an identity for the gain that solves K S = P H^T): row a of P - K G^T is P[a, :] (1 - K[a][a])
+// where P >> R, and 1 - K[a][a] = R / S carries K's rounding S / R times over (3e8 after a 100 s
+// gap before a fix).  M == N without GAIN_R keeps P - K G^T on every row: the A/B arm.
 template <int N, int M, bool DIAG_R, typename T, int NEWTON = 2, bool POISON = true, int NV = 1, bool JOSEPH = true,
           bool GAIN_R = false>
 __device__ __forceinline__ bool sel_update_nv(T (&xv)[NV][N], T (&P)[N * (N + 1) / 2], const T (&zv)[NV][M],
@@ -250,7 +260,7 @@ __device__ __forceinline__ bool sel_update_nv(T (&xv)[NV][N], T (&P)[N * (N + 1)
 #pragma unroll
         for (int i = 0; i < N; ++i)
 #pragma unroll
-            for (int j = i; j < N; ++j) P[tri<N>(i, j)] = K[i][j] * R[tri<M>(j, j)];
+            for (int j = i; j < N; ++j) P[tri<N>(i, j)] = K[j][i] * R[tri<M>(i, i)];
         return ok;
     }
     // Joseph: P+ = (I-KH) P (I-KH)^T + K R K^T = (P - K G^T) + E K^T with G = P H^T and
@@ -275,8 +285,12 @@ __device__ __forceinline__ bool sel_update_nv(T (&xv)[NV][N], T (&P)[N * (N + 1)
 #pragma unroll
         for (int j = i; j < N; ++j) {
             T s = P[tri<N>(i, j)];
+            if (!JOSEPH && DIAG_R && i < M && M < N) {
+                s = K[j][i] * R[tri<M>(i, i)];  // an observed row: (P+ H^T)^T = (K R)^T
+            } else {
 #pragma unroll
-            for (int b = 0; b < M; ++b) s = fmaT(-K[i][b], P[tri<N>(b, j)], s);
+                for (int b = 0; b < M; ++b) s = fmaT(-K[i][b], P[tri<N>(b, j)], s);
+            }
             if constexpr (JOSEPH) {
 #pragma unroll
                 for (int a = 0; a < M; ++a) s = fmaT(E[a], K[j][a], s);

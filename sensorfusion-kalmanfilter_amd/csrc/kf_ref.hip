@@ -48,7 +48,8 @@ constexpr int kGps = 0, kImu = 1;  // KF_EVENT_GPS / KF_EVENT_IMU; 2 = predict o
 // Newton steps on the update's pivot reciprocals (see sel_update)
 constexpr int kRefNewton = 1;
 // Covariance update of the reference models.  fp64 takes the reference's own form
-// P = (I - K H) P (kf_workers.py:711, hw5_2.py:358, 376) over the packed upper triangle; fp32 keeps
+// P = (I - K H) P (kf_workers.py:711, hw5_2.py:358, 376) over the packed upper triangle, its
+// observed rows as K R (sel_update_nv: the same value without 1 - K's cancellation); fp32 keeps
 // Joseph's, which the fp32 parity gate needs (the simple form drifts there).
 // KF_REF_JOSEPH_F64=1 builds fp64 with Joseph too (the A/B arm).
 #ifndef KF_REF_JOSEPH_F64
@@ -58,7 +59,7 @@ template <typename T>
 constexpr bool kRefJoseph = sizeof(T) == 4 || KF_REF_JOSEPH_F64 != 0;
 // The IMU pseudo-measurement's H = I chain updates take P = K R (sel_update_nv's GAIN_R: the
 // same value as (I - K)P, without its cancellation), in both precisions; KF_REF_GAIN_R=0 builds
-// the A/B arm without it.
+// the A/B arm without it (fp64: the cancelling P - K P on every row; fp32: Joseph's).
 #ifndef KF_REF_GAIN_R
 #define KF_REF_GAIN_R 1
 #endif
@@ -4553,8 +4554,10 @@ __device__ __forceinline__ void schedule_block_min(uint64_t& key, uint64_t& rank
     cnt = sc[0];
 }
 
+// waves_per_eu(3): the leaf instantiation sits at the 168-VGPR edge of three waves per SIMD
 template <bool CUSTOM, bool LEAF>
-__global__ __launch_bounds__(kBlock) void ref15_schedule_kernel(const ScheduleArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void ref15_schedule_kernel(
+    const ScheduleArgs a) {
     uint64_t bkey = ~uint64_t(0), brank = ~uint64_t(0), cnt = 0;
     const uint64_t stride = uint64_t(gridDim.x) * kBlock;
     const bool narrow = a.n_nodes <= 0xffffffffull;  // 32-bit divisions where the level allows
