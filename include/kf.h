@@ -415,6 +415,34 @@ int kf_run_sweep(kf_batch* handle, int T, const uint8_t* etype, const double* dt
                  const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
                  int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
 
+/* Parameter sweep: kf_run_sweep with noise constants per filter, so ONE launch runs the stream
+ * under B constant sets (a grid of process-noise scales, R_gps from 1 to 10, several thresholds
+ * per set) instead of one handle and one launch per set.  Every argument and output is
+ * kf_run_sweep's, with the same limits, and the call is asynchronous on `stream` and capturable
+ * in the same way; the addition is consts, device [R][B] double, filter index fastest, which the
+ * caller owns until the launch has run.  R = kf_consts_rows(model): the model's diagonal
+ * constants in kf_params order with its lengths, ref_q (15; REF8: 8), then ref_r_imu (15; 8),
+ * then ref_r_gps (3; 2): 33 rows for KF_MODEL_REF15, 18 for KF_MODEL_REF8.  Filter f runs the
+ * stream from its own column of the handle's state, gated by thresholds[f], with column f of
+ * consts in place of the handle's constants; each value is converted to the handle's dtype as
+ * the handle's own kf_params constants are.  P0 is not part of the table: it is whatever
+ * kf_set_state put in the handle.  thresholds may be NULL: every filter is -inf (always update).
+ * consts = NULL is kf_run_sweep itself (the same kernel; thresholds then must not be NULL).  The
+ * values are not validated (they live on the device): a constant that makes an innovation pivot
+ * non-positive fails that filter alone, KF_ENOTSPD in its status and NaN records from that event
+ * on, its neighbours untouched.  One more limit (KF_EINVAL before anything is queued): the
+ * table, R B 8 < 2 GiB.  Costs about one kf_run_sweep of the same B: a lane loads its chain's
+ * constants once, before the first event, and the event step is kf_run_sweep's.  Replaces one
+ * class_args dict of getters (kf_workers.py:1242-1251, the getters :519-614) and one
+ * run_adaptive_threshold_kalman_filter call per constant set. */
+int kf_run_sweep_params(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        const double* thresholds, const double* consts, void* traj, void* logdet, uint8_t* updated,
+                        int32_t* n_updated, int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
+
+/* Rows of kf_run_sweep_params' consts table for `model`: 33 for KF_MODEL_REF15 (ref_q 15, ref_r_imu
+ * 15, ref_r_gps 3), 18 for KF_MODEL_REF8 (8, 8, 2).  KF_EINVAL for any other model or NULL rows. */
+int kf_consts_rows(int model, int* rows);
+
 /* Ragged tails of ONE event stream in one launch: the handle's B filters are B independent gated
  * runs over different ranges of the same stream from different start states.  KF_MODEL_REF15 /
  * KF_MODEL_REF8.  etype / dt / payload: kf_run_sweep's device [T], [T], [T][9].  Tail f runs the

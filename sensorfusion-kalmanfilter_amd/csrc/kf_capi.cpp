@@ -1010,25 +1010,31 @@ int kf_run_events_gates(kf_batch* h, int T, const uint8_t* etype, const double* 
                              thresholds);
 }
 
-int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
-                 const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
-                 int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream) {
+// kf_run_sweep and kf_run_sweep_params (consts != nullptr: filter f under column f of the table)
+static int run_sweep_impl(const char* fn, kf_batch* h, int T, const uint8_t* etype, const double* dt,
+                          const void* payload, const double* thresholds, const double* consts, void* traj, void* logdet,
+                          uint8_t* updated, int32_t* n_updated, int ckpt_every, void* ckpt_x, void* ckpt_P,
+                          void* stream) {
     if (int rc = check_handle(h)) return rc;
-    if (!is_ref(h)) return fail(KF_EINVAL, "kf_run_sweep: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle");
-    if (T < 0) return fail(KF_EINVAL, "kf_run_sweep: T = %d < 0", T);
-    if (ckpt_every < 0) return fail(KF_EINVAL, "kf_run_sweep: ckpt_every = %d < 0", ckpt_every);
+    if (!is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle", fn);
+    if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
+    if (ckpt_every < 0) return fail(KF_EINVAL, "%s: ckpt_every = %d < 0", fn, ckpt_every);
     if (T == 0 || h->B == 0) return KF_OK;
-    if (!etype || !dt || !payload) return fail(KF_EINVAL, "kf_run_sweep: null etype/dt/payload stream");
-    if (!thresholds) return fail(KF_EINVAL, "kf_run_sweep: null thresholds");
+    if (!etype || !dt || !payload) return fail(KF_EINVAL, "%s: null etype/dt/payload stream", fn);
+    if (!thresholds && !consts) return fail(KF_EINVAL, "%s: null thresholds", fn);
     if (ckpt_every > 0 && T >= ckpt_every && (!ckpt_x || !ckpt_P))
-        return fail(KF_EINVAL, "kf_run_sweep: null ckpt_x/ckpt_P with %d checkpoints to write", T / ckpt_every);
+        return fail(KF_EINVAL, "%s: null ckpt_x/ckpt_P with %d checkpoints to write", fn, T / ckpt_every);
     // the kernel's descriptors: the stream by byte range (32-bit), the state rows as one span
     // whose offsets keep bit 31 free for dropped lanes; records and checkpoints per event
     const uint64_t w = elem(h);
     if (uint64_t(T) * 9u * w >= (uint64_t(1) << 32))
-        return fail(KF_EINVAL, "kf_run_sweep: T = %d events exceed the 4 GiB payload descriptor (9 T w)", T);
+        return fail(KF_EINVAL, "%s: T = %d events exceed the 4 GiB payload descriptor (9 T w)", fn, T);
     if (uint64_t(h->B) * 27u * w >= (uint64_t(1) << 31))
-        return fail(KF_EINVAL, "kf_run_sweep: B = %lld filters exceed the 2 GiB state span (27 B w)", (long long)h->B);
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB state span (27 B w)", fn, (long long)h->B);
+    const int model = h->model == KF_MODEL_REF15 ? 15 : 8;
+    if (consts && uint64_t(kfmi::consts_rows(model)) * uint64_t(h->B) * 8u >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB constants table (%d B 8)", fn, (long long)h->B,
+                    kfmi::consts_rows(model));
     kfmi::SweepArgs a{};
     a.B = h->B;
     a.T = T;
@@ -1047,9 +1053,35 @@ int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, con
     a.ckpt_x = ckpt_x;
     a.ckpt_P = ckpt_P;
     a.kc = h->kc;
-    hipError_t e = kfmi::launch_ref_sweep(h->model == KF_MODEL_REF15 ? 15 : 8, h->dtype == KF_F64, a,
-                                          static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? KF_OK : hip_fail(e, "kf_run_sweep");
+    a.consts = consts;
+    hipError_t e = kfmi::launch_ref_sweep(model, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
+int kf_run_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                 const double* thresholds, void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
+                 int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream) {
+    return run_sweep_impl("kf_run_sweep", h, T, etype, dt, payload, thresholds, nullptr, traj, logdet, updated,
+                          n_updated, ckpt_every, ckpt_x, ckpt_P, stream);
+}
+
+int kf_run_sweep_params(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        const double* thresholds, const double* consts, void* traj, void* logdet, uint8_t* updated,
+                        int32_t* n_updated, int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream) {
+    if (!consts)  // kf_run_sweep itself: the handle's constants
+        return kf_run_sweep(h, T, etype, dt, payload, thresholds, traj, logdet, updated, n_updated, ckpt_every, ckpt_x,
+                            ckpt_P, stream);
+    return run_sweep_impl("kf_run_sweep_params", h, T, etype, dt, payload, thresholds, consts, traj, logdet, updated,
+                          n_updated, ckpt_every, ckpt_x, ckpt_P, stream);
+}
+
+int kf_consts_rows(int model, int* rows) {
+    if (!is_ref(model))
+        return fail(KF_EINVAL, "kf_consts_rows: model %d has no per-filter constants (KF_MODEL_REF15 or KF_MODEL_REF8)",
+                    model);
+    if (!rows) return fail(KF_EINVAL, "kf_consts_rows: null rows");
+    *rows = kfmi::consts_rows(model == KF_MODEL_REF15 ? 15 : 8);
+    return KF_OK;
 }
 
 int kf_run_tails(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload, const int32_t* lo,

@@ -137,10 +137,21 @@ struct SweepArgs {
     // (ckpt_x / ckpt_P's layout with src_B columns; src_row = -1: the handle's own column f), and
     // writes no records and no checkpoints
     const TailSpec* tails;   // device [B]
-    const void* src_x;       // [R][N][src_B]
+    // Parameter sweep (kf_run_sweep_params; the PARAMS instantiations only, which have no tails:
+    // the pointer shares src_x's slot, so the argument block of the other instantiations is what
+    // it was): filter f's own noise constants, column f of a device table [consts_rows(model)][B]
+    // of doubles: the q of every state, then r_imu, then r_gps, in RefConsts' order with the
+    // model's lengths.  thresholds may then be nullptr (every filter -inf); kc is not read (P0
+    // is the caller's kf_set_state)
+    union {
+        const void* src_x;     // [R][N][src_B]
+        const double* consts;  // [consts_rows][B]
+    };
     const void* src_P;       // [R][NBLK][src_B]
     int64_t src_B;
 };
+// rows of SweepArgs::consts: q [N], r_imu [N], r_gps [NP]
+constexpr int consts_rows(int model) { return model == 15 ? 33 : 18; }
 
 // Time-parallel run of one filter over a long event stream (kf_run_stream): the state banks of
 // the three chunk passes and the check.  Bank layouts are the handle's ([N][B], [NBLK][B]).
@@ -469,7 +480,8 @@ hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t 
 // the chain kernel in stream mode (a.s_len > 0); nv = 4: the map pass, four state variants per
 // filter sharing its covariance (state bank of 4 B columns)
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv = 1);
-// one stream under the handle's B thresholds (ref_sweep_kernel: 8 lanes per filter)
+// one stream under the handle's B thresholds (ref_sweep_kernel: 8 lanes per filter); a.consts set:
+// under B constant sets too (its PARAMS instantiations)
 hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream);
 // ragged tails of one stream (ref_sweep_kernel's TAILS instantiations; a.tails set, a.T >= 0)
 hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream);

@@ -769,6 +769,12 @@ struct ChainIn {
     T va, vb;
 };
 
+// Column f of a parameter sweep's constants table [2 N + NP][B] (SweepArgs::consts)
+struct ConstsColumn {
+    const double* table;
+    int64_t B, f;
+};
+
 // One lane of the 8-lanes-per-filter kernels (ref_chain_kernel, ref_sweep_kernel,
 // ref_chain_gated_kernel): which chain lane c of a group runs, where that chain's states, block
 // rows and payload columns are, its noise constants, and the event all three kernels run.  The
@@ -808,6 +814,33 @@ struct ChainLane {
                 }
             if (pva) Rgps = T(ro(kc)->r_gps[ca]);
         }
+    }
+
+    // The lane of filter f of a parameter sweep (ref_sweep_kernel's PARAMS): its chain's constants
+    // from column f of the table consts [2 N + NP][B] (rows: q per state, r_imu per state, r_gps
+    // per axis), converted as the CUSTOM constants are.  Plain per-lane vector loads, every one in
+    // bounds: a lane without the state reads row 0 of the section and keeps the literal (an aw
+    // lane's inert third state: Q = 0, R = 1).
+    __device__ __forceinline__ ChainLane(int lane, const ConstsColumn& col)
+        : ChainLane(lane, static_cast<const RefConsts*>(nullptr)) {
+        static_assert(!CUSTOM, "the table replaces the handle's constants");
+        const double* consts = col.table;
+        const int64_t B = col.B, f = col.f;
+        double tq[3], tr[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int row = xi[k] >= 0 ? xi[k] : 0;
+            tq[k] = consts[int64_t(row) * B + f];
+            tr[k] = consts[int64_t(M::N + row) * B + f];
+        }
+        const double tg = consts[int64_t(2 * M::N + (pva ? ca : 0)) * B + f];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (xi[k] >= 0) {
+                q[k] = T(tq[k]);
+                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(tr[k]);
+            }
+        if (pva) Rgps = T(tg);
     }
 
     // P[k] where the lane holds no row k: the identity (an aw lane's inert state has variance 1)
@@ -1223,6 +1256,12 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 // branches diverge between groups (a group is active or inactive as a whole: its DPP reductions
 // stay legal).  The wave runs to its longest tail with the finished groups predicated off, and
 // the input ring clamps per group to the tail's own last event; an empty tail loads nothing.
+//
+// PARAMS (kf_run_sweep_params): the groups differ in their noise constants as well.  Lane set-up
+// fills the lane's q / Rimu / Rgps from column f of a.consts (ChainLane's table constructor)
+// instead of the literals or the handle's scalars, once, beside the threshold and before the
+// ring's prologue, whose drain covers those loads too; a.thresholds may be null (every group
+// -inf).  Everything after set-up is the sweep's: the ring, ChainLane::event, the records.
 // ------------------------------------------------------------------------------------
 #ifndef KF_SWEEP_DEPTH
 #define KF_SWEEP_DEPTH 4
@@ -1230,8 +1269,17 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 constexpr int kSweepDepth = KF_SWEEP_DEPTH;  // input ring of ref_sweep_kernel
 constexpr int kSweepBlock = 64;              // one wave (8 thresholds) per workgroup: waves spread over the CUs
 
-template <typename T, class M, bool CUSTOM, bool TAILS = false>
+// where group f's lanes take their constants from: the handle's, or PARAMS: column f of the table
+template <bool PARAMS>
+__device__ __forceinline__ auto sweep_consts(const SweepArgs& a, int64_t f) {
+    if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
+    else return a.kc;
+}
+
+template <typename T, class M, bool CUSTOM, bool TAILS = false, bool PARAMS = false>
 __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs a) {
+    static_assert(!PARAMS || (!TAILS && !CUSTOM), "per-filter constants: the plain sweep, in place of the handle's");
+    static_assert(consts_rows(M::N) == 2 * M::N + M::NP, "the table's rows: q, r_imu, r_gps");
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
     const int64_t f = g / kGroup;
     // TAILS: the group's tail, and the wave's longest (every lane of the wave takes part in the
@@ -1249,7 +1297,7 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
         wave_len = wave_uniform(wave_len);
     }
     if (f >= a.B) return;  // whole groups leave together
-    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), a.kc);
+    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), sweep_consts<PARAMS>(a, f));
     const int c = L.c;
     const bool live = L.live;
     const auto& xi = L.xi;
@@ -1292,7 +1340,7 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     // the group's threshold; NaN never opens the gate (every comparison with it is false), and
     // -inf is "always update": the gate is not evaluated (a covariance that is not positive
     // definite has no log-det to compare, and the reference's slogdet still passes -inf there)
-    const double thr_d = a.thresholds[f];
+    const double thr_d = (PARAMS && !a.thresholds) ? -__builtin_inf() : a.thresholds[f];
     const T thr = T(thr_d);
     const bool always = thr_d == -__builtin_inf();
     GateBand<T> gate;
@@ -4835,9 +4883,12 @@ hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t
 }
 
 hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
-    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8)) return hipErrorInvalidValue;
+    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || (!a.thresholds && !a.consts)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
+    if (a.consts)
+        KF_MODEL_DISPATCH(model, f64, ref_sweep_kernel<T, M, false, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
+    else
+        KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
     return hipGetLastError();
 }
 

@@ -61,6 +61,27 @@ def default_params(model):
     return p
 
 
+def consts_rows(model):
+    """Rows R of run_sweep's ``consts`` table for a reference model (kf_consts_rows): q per state,
+    then r_imu per state, then r_gps per axis; 33 for 'ref15', 18 for 'ref8'."""
+    n = ctypes.c_int(0)
+    check(_lib.lib().kf_consts_rows(MODELS[model][0], ctypes.byref(n)))
+    return n.value
+
+
+def consts_table(model, sets):
+    """The [R, B] float64 table of B constant sets (kfmi.ref15.ModelConsts of ``model``): column f
+    is sets[f]'s q, r_imu, r_gps.  Their P0 is not part of it (set_state carries it)."""
+    for c in sets:
+        if getattr(c, 'model', None) != model:
+            raise KFError(_lib.KF_EINVAL, f'consts: a constant set of model {getattr(c, "model", None)!r} for a '
+                                          f'{model} handle')
+    tab = np.empty((consts_rows(model), len(sets)), np.float64)
+    for f, c in enumerate(sets):
+        tab[:, f] = np.concatenate([c.q, c.r_imu, c.r_gps])
+    return tab
+
+
 def device_count():
     n = ctypes.c_int(0)
     check(_lib.lib().kf_device_count(ctypes.byref(n)))
@@ -414,7 +435,7 @@ class BatchedKF:
         return tr, ld, up, cv
 
     def run_sweep(self, etype, dt, payload, thresholds, traj=True, logdet=True, updated=False, counts=True,
-                  checkpoint_every=0):
+                  checkpoint_every=0, consts=None):
         """ONE event stream under this handle's B adaptive gates in one launch (kf_run_sweep):
         etype [T] uint8, dt [T] float64, payload [T, 9]; filter f runs every event from its own
         state in the handle and updates only where logdet(P_pred) > thresholds[f] ([B] float64;
@@ -422,9 +443,36 @@ class BatchedKF:
         n_updated [B] int32, ckpt_x [C, n, B], ckpt_P [C, rows, B]) with None for outputs not
         asked for; C = T // checkpoint_every, row c the filters after event (c + 1) *
         checkpoint_every - 1 (set_state(ckpt_x[c], ckpt_P[c]) and a sweep over the events after
-        it continue the run bit for bit)."""
+        it continue the run bit for bit).
+
+        ``consts``: noise constants per filter (kf_run_sweep_params), a [R, B] float64 table (R =
+        consts_rows(model): q, r_imu, r_gps per state, filter index fastest) or a list of B
+        kfmi.ref15.ModelConsts; filter f then runs under column f instead of the handle's
+        constants (its P0 is the caller's set_state), and ``thresholds`` may be None: every filter
+        always updates.  A table of another dtype or shape and a list of another length are
+        KFError(KF_EINVAL)."""
         if self.model not in REF_MODELS:
             raise ValueError('run_sweep needs a ref15 or ref8 handle')
+        tab = None
+        if consts is not None:
+            R = consts_rows(self.model)
+            if isinstance(consts, (list, tuple)):
+                if len(consts) != self.batch:
+                    raise KFError(_lib.KF_EINVAL, f'consts: {len(consts)} constant sets for B = {self.batch} filters')
+                consts = consts_table(self.model, consts)
+            if isinstance(consts, np.ndarray):
+                consts = torch.from_numpy(np.ascontiguousarray(consts))
+            if not torch.is_tensor(consts):
+                raise TypeError(f'consts: expected a tensor, an array or a list of ModelConsts, got {type(consts)}')
+            if consts.dtype != torch.float64:
+                raise KFError(_lib.KF_EINVAL, f'consts: dtype {consts.dtype} != torch.float64 (the table is float64 '
+                                              f'for every handle dtype; the kernel converts)')
+            if tuple(consts.shape) != (R, self.batch):
+                raise KFError(_lib.KF_EINVAL, f'consts: shape {tuple(consts.shape)} != expected {(R, self.batch)} '
+                                              f'([R, B], R = {R} rows for {self.model})')
+            tab = self._dev(consts, (R, self.batch), 'consts', torch.float64)
+        elif thresholds is None:
+            raise ValueError('run_sweep: thresholds may be None only with consts')
         T = int(etype.shape[0])
         every = int(checkpoint_every)
         if every < 0:
@@ -432,7 +480,7 @@ class BatchedKF:
         et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
         dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
         pay = self._dev(payload.reshape(T, 9), (T, 9), 'payload')
-        thr = self._dev(thresholds, (self.batch,), 'thresholds', torch.float64)
+        thr = self._dev(thresholds, (self.batch,), 'thresholds', torch.float64) if thresholds is not None else None
         tr = self.empty(T, TRAJ_WIDTH[self.model], self.batch) if traj else None
         ld = self.empty(T, self.batch) if logdet else None
         up = torch.empty(T, self.batch, dtype=torch.uint8, device=self.device) if updated else None
@@ -440,9 +488,13 @@ class BatchedKF:
         C = T // every if every > 0 else 0
         cx = self.empty(C, self.n, self.batch) if every > 0 else None
         cP = self.empty(C, self.ntri, self.batch) if every > 0 else None
-        check(_lib.lib().kf_run_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tr), _ptr(ld),
-                                      _ptr(up), _ptr(nu), every, _ptr(cx) if C else None, _ptr(cP) if C else None,
-                                      self._stream()))
+        ck = (every, _ptr(cx) if C else None, _ptr(cP) if C else None, self._stream())
+        if tab is None:
+            check(_lib.lib().kf_run_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tr),
+                                          _ptr(ld), _ptr(up), _ptr(nu), *ck))
+        else:
+            check(_lib.lib().kf_run_sweep_params(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tab),
+                                                 _ptr(tr), _ptr(ld), _ptr(up), _ptr(nu), *ck))
         return tr, ld, up, nu, cx, cP
 
     def run_tails(self, etype, dt, payload, lo, hi, thresholds, src_x=None, src_P=None, src_row=None, src_col=None,

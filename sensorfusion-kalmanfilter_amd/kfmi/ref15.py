@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import BatchedKF
+from .engine import BatchedKF, consts_table
 
 GPS, IMU, PREDICT, NONE = _lib.KF_EVENT_GPS, _lib.KF_EVENT_IMU, _lib.KF_EVENT_PREDICT, _lib.KF_EVENT_NONE
 
@@ -675,6 +675,14 @@ class AdaptiveSweep:
         self._prev = self._t[last]
         self._x0 = torch.as_tensor(x0[:, None], dtype=tdt, device=dev)
         self._P0 = torch.as_tensor(to_blocks(P)[:, None], dtype=tdt, device=dev)
+        # ParameterSweep: a constant set per filter, [R, B] on the device, and on a cold start each
+        # set's own P0 as that filter's column
+        sets = getattr(self, '_sets', None)
+        self._table = None
+        if sets is not None:
+            self._table = torch.from_numpy(consts_table('ref15', sets)).to(dev)
+            if not warm:
+                self._P0 = torch.as_tensor(np.stack([to_blocks(c.P0) for c in sets], 1), dtype=tdt, device=dev)
         self._kf1 = None
         if self.empty:
             return
@@ -683,7 +691,7 @@ class AdaptiveSweep:
             kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
             (self._traj, self._ld, self._up, nu, self._cx, self._cP) = kf.run_sweep(
                 self._et, self._dt, self._pay, torch.from_numpy(self.thresholds), traj=self.records,
-                logdet=self.records, updated=self.records, checkpoint_every=self.every)
+                logdet=self.records, updated=self.records, checkpoint_every=self.every, consts=self._table)
             self._x, self._Pb = kf.state()
             self._status = kf.status()
             self.n_updates = nu.cpu().numpy().astype(np.int64)
@@ -738,14 +746,15 @@ class AdaptiveSweep:
         if c >= 0:
             x, Pb, lo = self._cx[c][:, i:i + 1], self._cP[c][:, i:i + 1], (c + 1) * self.every
         else:
-            x, Pb, lo = self._x0, self._P0, 0
+            x, Pb, lo = self._x0, self._P0[:, i:i + 1] if self._P0.shape[1] > 1 else self._P0, 0
         if n > lo:
             if self._kf1 is None:
                 self._kf1 = BatchedKF('ref15', 1, self.dtype, device=self.dev.index or 0, params=_params(self.consts))
             kf = self._kf1
             kf.set_state(x.contiguous(), Pb.contiguous())
             kf.run_sweep(self._et[lo:n], self._dt[lo:n], self._pay[lo:n], self.thresholds[i:i + 1], traj=False,
-                         logdet=False, counts=False)
+                         logdet=False, counts=False,
+                         consts=self._table[:, i:i + 1].contiguous() if self._table is not None else None)
             x, Pb = kf.state()
         xs = x[:6, 0].double().cpu().numpy()
         prev = float(self._prev[n - 1])
@@ -799,6 +808,47 @@ class AdaptiveSweep:
 def run_adaptive_threshold_sweep(events, thresholds, **kw):
     """The AdaptiveSweep of ``events`` under ``thresholds`` (its keyword arguments)."""
     return AdaptiveSweep(events, thresholds, **kw)
+
+
+class ParameterSweep(AdaptiveSweep):
+    """run_adaptive_threshold_kalman_filter over ONE window under every constant set of
+    ``consts_list`` (ModelConsts('ref15', ...): the getters a caller of the reference replaces
+    through class_args, kf_workers.py:1242-1251) at once: one kf_run_sweep_params launch, filter i
+    under consts_list[i] and thresholds[i] (None: no gate, every event updates), instead of one
+    handle and one run per set.  The window, the drivers' rules and the arrays are
+    AdaptiveSweep's.  A cold start takes each set's own P0 (a column of the start state); a warm
+    start (initial_pt, initial_state) is shared by every filter.
+
+    ``result(i)``: the 5-tuple run_adaptive_threshold_kalman_filter(..., R_threshold=thresholds[i],
+    consts=consts_list[i]) returns.  ``warm_start(i, end_idx)``: its prefix's (states[-1], P,
+    previous_time), the tail past the checkpoint run as a one-filter parameter sweep with set i's
+    column, so it rounds as the sweep did.  ``warm_starts`` is the list of those (kf_run_tails
+    has no per-filter constants: one launch per tail)."""
+
+    def __init__(self, events, consts_list, thresholds=None, start_idx=None, end_idx=None, initial_pt=None,
+                 initial_state=None, dtype='f64', device=0, records=True, checkpoint_every=4096):
+        self._sets = list(consts_list)
+        if thresholds is None:
+            thresholds = np.full(len(self._sets), -np.inf)
+        if len(np.reshape(thresholds, -1)) != len(self._sets):
+            raise _lib.KFError(_lib.KF_EINVAL, f'ParameterSweep: {len(np.reshape(thresholds, -1))} thresholds for '
+                                               f'{len(self._sets)} constant sets')
+        for c in self._sets:
+            if not isinstance(c, ModelConsts) or c.model != 'ref15':
+                raise ValueError('ParameterSweep: consts_list holds ModelConsts(\'ref15\', ...)')
+        super().__init__(events, thresholds, start_idx, end_idx, initial_pt, initial_state, dtype, device, None,
+                         records, checkpoint_every)
+        self.consts_list = self._sets
+
+    def warm_starts(self, index, end_idxs):
+        if len(index) != len(end_idxs):
+            raise ValueError(f'warm_starts: {len(index)} constant sets for {len(end_idxs)} end points')
+        return [self.warm_start(int(i), e) for i, e in zip(index, end_idxs)]
+
+
+def run_parameter_sweep(events, consts_list, thresholds=None, **kw):
+    """The ParameterSweep of ``events`` under ``consts_list`` (its keyword arguments)."""
+    return ParameterSweep(events, consts_list, thresholds, **kw)
 
 
 def run_kalman_filter(events, start_idx, end_idx, dtype='f64', device=0, consts=None):
