@@ -439,6 +439,54 @@ int kf_run_sweep_params(kf_batch* handle, int T, const uint8_t* etype, const dou
                         const double* thresholds, const double* consts, void* traj, void* logdet, uint8_t* updated,
                         int32_t* n_updated, int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
 
+/* Scored parameter sweep: kf_run_sweep_params that also ranks its filters, so a noise study gets
+ * one number per constant set from the launch that runs the sets, not from a [T][6][B] trajectory
+ * record reduced afterwards (57 B per event and filter) and not at all for the innovation
+ * statistics, which no record holds.  Every argument shared with kf_run_sweep_params means what it
+ * means there (layouts, limits, gate conventions, NONE / PREDICT events, checkpoints, asynchronous
+ * on `stream`, capturable), and the records, counts, checkpoints, end state and status are that
+ * call's bit for bit: being scored does not change the filter.  consts is mandatory here (NULL is
+ * KF_EINVAL; a threshold sweep under one set passes equal columns); thresholds may be NULL.
+ *
+ * scores: device [KF_SCORE_ROWS][B] double, filter index fastest, not NULL, overwritten.  Doubles
+ * for every handle dtype, the counts too (exact below 2^53).  Rows 0-5 are sums over the APPLIED
+ * updates of each sensor (a shut gate, PREDICT and NONE events add nothing) of the event step's
+ * own innovation: S = H P_pred H^T + R after the predict, y = z - H x_pred with z the fix or the
+ * IMU pseudo-measurement built from the predicted state (kf_workers.py:698-706); NIS is y^T S^-1 y
+ * and 0.5 (NIS + logdet_S + n m log 2 pi) is the Gaussian innovation negative log-likelihood (m =
+ * 3 | 2 per fix, 15 | 8 per IMU event).  P is block-diagonal over the axis chains and R diagonal,
+ * so each chain adds its own w^T D^-1 w (w = L^-1 y) and its own pivots from the LDL^T the update
+ * solves with anyway.
+ *
+ * track: device [T][3] double or NULL.  Row t is the reference position at event t (KF_MODEL_REF8
+ * reads columns 0 and 1).  Event t is scored after its step, whatever its type (a NONE event
+ * scores the unchanged state), when every column the model reads is not NaN; a NaN row is "no
+ * reference here".  The position is converted to double, then differenced, squared and summed in
+ * double.  track = NULL leaves rows 6 and 7 at 0.
+ *
+ * A filter whose status is not KF_OK when the launch ends has NaN in rows 1, 2, 4, 5 and 7 (its
+ * counts still count); its neighbours' scores are untouched.  The scores are the same bits on
+ * every run and do not depend on B, on the filter's place in its wave or on which record pointers
+ * are NULL: each lane sums its chain's terms in event order in double (det S as a running
+ * mantissa-exponent product of the pivots, logged once), then one fixed reduction over the
+ * filter's lanes per row; no atomics.  T = 0 zeroes scores.  One more limit (KF_EINVAL before
+ * anything is queued): the track, 24 T < 4 GiB.  Replaces, per constant set, the class_args
+ * getter replacement (kf_workers.py:1242-1251) followed by calculate_accuracy_metrics
+ * (kf_workers.py:1162-1216) on the run's states. */
+#define KF_SCORE_GPS_N        0   /* applied GPS updates                                      */
+#define KF_SCORE_GPS_NIS      1   /* sum over them of y^T S^-1 y                              */
+#define KF_SCORE_GPS_LOGDET_S 2   /* sum over them of log det S                               */
+#define KF_SCORE_IMU_N        3
+#define KF_SCORE_IMU_NIS      4
+#define KF_SCORE_IMU_LOGDET_S 5
+#define KF_SCORE_POS_N        6   /* events scored against the track                          */
+#define KF_SCORE_POS_SSE      7   /* sum over them of sum_axis (x[axis] - track[t][axis])^2   */
+#define KF_SCORE_ROWS         8
+int kf_run_sweep_scores(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        const double* thresholds, const double* consts, const double* track, double* scores,
+                        void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
+                        int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
+
 /* Rows of kf_run_sweep_params' consts table for `model`: 33 for KF_MODEL_REF15 (ref_q 15, ref_r_imu
  * 15, ref_r_gps 3), 18 for KF_MODEL_REF8 (8, 8, 2).  KF_EINVAL for any other model or NULL rows. */
 int kf_consts_rows(int model, int* rows);

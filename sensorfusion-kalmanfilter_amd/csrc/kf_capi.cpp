@@ -1010,15 +1010,30 @@ int kf_run_events_gates(kf_batch* h, int T, const uint8_t* etype, const double* 
                              thresholds);
 }
 
-// kf_run_sweep and kf_run_sweep_params (consts != nullptr: filter f under column f of the table)
+static_assert(KF_SCORE_GPS_N == kfmi::kScoreGpsN && KF_SCORE_GPS_NIS == kfmi::kScoreGpsNis &&
+                  KF_SCORE_GPS_LOGDET_S == kfmi::kScoreGpsLogdetS && KF_SCORE_IMU_N == kfmi::kScoreImuN &&
+                  KF_SCORE_IMU_NIS == kfmi::kScoreImuNis && KF_SCORE_IMU_LOGDET_S == kfmi::kScoreImuLogdetS &&
+                  KF_SCORE_POS_N == kfmi::kScorePosN && KF_SCORE_POS_SSE == kfmi::kScorePosSse &&
+                  KF_SCORE_ROWS == kfmi::kScoreRows,
+              "kf.h's score rows are the kernel's");
+
+// kf_run_sweep, kf_run_sweep_params (consts != nullptr: filter f under column f of the table) and
+// kf_run_sweep_scores (scores != nullptr: the scored instantiations; consts then mandatory)
 static int run_sweep_impl(const char* fn, kf_batch* h, int T, const uint8_t* etype, const double* dt,
                           const void* payload, const double* thresholds, const double* consts, void* traj, void* logdet,
                           uint8_t* updated, int32_t* n_updated, int ckpt_every, void* ckpt_x, void* ckpt_P,
-                          void* stream) {
+                          void* stream, const double* track = nullptr, double* scores = nullptr) {
     if (int rc = check_handle(h)) return rc;
     if (!is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle", fn);
     if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
     if (ckpt_every < 0) return fail(KF_EINVAL, "%s: ckpt_every = %d < 0", fn, ckpt_every);
+    if (scores && uint64_t(T) * 24u >= (uint64_t(1) << 32))
+        return fail(KF_EINVAL, "%s: T = %d events exceed the 4 GiB track descriptor (24 T)", fn, T);
+    if (scores && T == 0 && h->B > 0) {  // no event: every row 0
+        hipError_t e = hipMemsetAsync(scores, 0, size_t(KF_SCORE_ROWS) * size_t(h->B) * sizeof(double),
+                                      static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+    }
     if (T == 0 || h->B == 0) return KF_OK;
     if (!etype || !dt || !payload) return fail(KF_EINVAL, "%s: null etype/dt/payload stream", fn);
     if (!thresholds && !consts) return fail(KF_EINVAL, "%s: null thresholds", fn);
@@ -1054,7 +1069,12 @@ static int run_sweep_impl(const char* fn, kf_batch* h, int T, const uint8_t* ety
     a.ckpt_P = ckpt_P;
     a.kc = h->kc;
     a.consts = consts;
-    hipError_t e = kfmi::launch_ref_sweep(model, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream));
+    if (scores) {
+        a.track = track;
+        a.scores = scores;
+    }
+    hipError_t e = kfmi::launch_ref_sweep(model, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream),
+                                          scores != nullptr);
     return e == hipSuccess ? KF_OK : hip_fail(e, fn);
 }
 
@@ -1073,6 +1093,17 @@ int kf_run_sweep_params(kf_batch* h, int T, const uint8_t* etype, const double* 
                             ckpt_P, stream);
     return run_sweep_impl("kf_run_sweep_params", h, T, etype, dt, payload, thresholds, consts, traj, logdet, updated,
                           n_updated, ckpt_every, ckpt_x, ckpt_P, stream);
+}
+
+int kf_run_sweep_scores(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                        const double* thresholds, const double* consts, const double* track, double* scores,
+                        void* traj, void* logdet, uint8_t* updated, int32_t* n_updated, int ckpt_every, void* ckpt_x,
+                        void* ckpt_P, void* stream) {
+    if (int rc = check_handle(h)) return rc;
+    if (!consts) return fail(KF_EINVAL, "kf_run_sweep_scores: null consts (a table is mandatory; equal columns for one set)");
+    if (!scores) return fail(KF_EINVAL, "kf_run_sweep_scores: null scores");
+    return run_sweep_impl("kf_run_sweep_scores", h, T, etype, dt, payload, thresholds, consts, traj, logdet, updated,
+                          n_updated, ckpt_every, ckpt_x, ckpt_P, stream, track, scores);
 }
 
 int kf_consts_rows(int model, int* rows) {

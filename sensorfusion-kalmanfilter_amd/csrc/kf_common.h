@@ -186,10 +186,19 @@ __device__ __forceinline__ T logdet_ldl(const T (&P)[N * (N + 1) / 2]) {
 // (an identity for the gain that solves K S = P H^T): row a of P - K G^T is P[a, :] (1 - K[a][a])
 // where P >> R, and 1 - K[a][a] = R / S carries K's rounding S / R times over (3e8 after a 100 s
 // gap before a fix).  M == N without GAIN_R keeps P - K G^T on every row: the A/B arm.
+// INNOV (opt-in; the default compiles to what it did): the update's own innovation statistics to
+// *innov, from variant 0's y and the factors S = L D L^T this update solves with anyway:
+// nis = sum_a w_a^2 / d_a with w = L^-1 y (that is y^T S^-1 y) and the pivots d[a] (their product
+// is det S).
+template <typename T, int M>
+struct Innov {
+    T nis, d[M];  // y^T S^-1 y and the LDL^T pivots of S
+};
+
 template <int N, int M, bool DIAG_R, typename T, int NEWTON = 2, bool POISON = true, int NV = 1, bool JOSEPH = true,
-          bool GAIN_R = false>
+          bool GAIN_R = false, bool INNOV = false>
 __device__ __forceinline__ bool sel_update_nv(T (&xv)[NV][N], T (&P)[N * (N + 1) / 2], const T (&zv)[NV][M],
-                                              const T (&R)[M * (M + 1) / 2]) {
+                                              const T (&R)[M * (M + 1) / 2], Innov<T, M>* innov = nullptr) {
     constexpr int MT = M * (M + 1) / 2;
     // S = H P H^T + R, then its LDL^T
     T S[MT];
@@ -248,6 +257,22 @@ __device__ __forceinline__ bool sel_update_nv(T (&xv)[NV][N], T (&P)[N * (N + 1)
         T y[M];
 #pragma unroll
         for (int a = 0; a < M; ++a) y[a] = zv[v][a] - xv[v][a];
+        if constexpr (INNOV) {
+            if (v == 0) {
+                T w[M];
+                T nis = T(0);
+#pragma unroll
+                for (int a = 0; a < M; ++a) {
+                    T s = y[a];
+#pragma unroll
+                    for (int b = 0; b < a; ++b) s = fmaT(-L[a][b], w[b], s);
+                    w[a] = s;
+                    nis = fmaT(s * s, dinv[a], nis);
+                    innov->d[a] = d[a];
+                }
+                innov->nis = nis;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             T s = xv[v][i];

@@ -147,8 +147,30 @@ struct SweepArgs {
         const void* src_x;     // [R][N][src_B]
         const double* consts;  // [consts_rows][B]
     };
-    const void* src_P;       // [R][NBLK][src_B]
-    int64_t src_B;
+    // Scored parameter sweep (kf_run_sweep_scores; the SCORE instantiations only, PARAMS ones, so
+    // no tails either: the two pointers share src_P's and src_B's slots the same way): the
+    // reference track, [T][3] doubles or nullptr, and the score rows out, [kScoreRows][B] doubles
+    union {
+        const void* src_P;     // [R][NBLK][src_B]
+        const double* track;   // [T][3]
+    };
+    union {
+        int64_t src_B;
+        double* scores;        // [kScoreRows][B]
+    };
+};
+static_assert(sizeof(int64_t) == sizeof(double*), "scores shares src_B's slot");
+// rows of SweepArgs::scores (kf.h's KF_SCORE_*; kf_capi.cpp asserts they agree)
+enum : int {
+    kScoreGpsN = 0,
+    kScoreGpsNis = 1,
+    kScoreGpsLogdetS = 2,
+    kScoreImuN = 3,
+    kScoreImuNis = 4,
+    kScoreImuLogdetS = 5,
+    kScorePosN = 6,
+    kScorePosSse = 7,
+    kScoreRows = 8
 };
 // rows of SweepArgs::consts: q [N], r_imu [N], r_gps [NP]
 constexpr int consts_rows(int model) { return model == 15 ? 33 : 18; }
@@ -482,7 +504,8 @@ hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t 
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv = 1);
 // one stream under the handle's B thresholds (ref_sweep_kernel: 8 lanes per filter); a.consts set:
 // under B constant sets too (its PARAMS instantiations)
-hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream);
+// scored: its SCORE instantiations (kf_run_sweep_scores; a.consts and a.scores set)
+hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream, bool scored = false);
 // ragged tails of one stream (ref_sweep_kernel's TAILS instantiations; a.tails set, a.T >= 0)
 hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream);
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream);

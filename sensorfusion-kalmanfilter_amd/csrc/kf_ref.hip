@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "kf_common.h"
 #include "kf_internal.h"
@@ -769,6 +770,40 @@ struct ChainIn {
     T va, vb;
 };
 
+// A scored sweep's event (ref_sweep_kernel's SCORE): the track row too, the lane's own column first
+template <typename T>
+struct ChainInScored : ChainIn<T> {
+    double track[3];
+};
+
+// What one lane of a scored sweep accumulates for its own chain, in event order: the NIS terms
+// and the position error in double, and det S as a running (mantissa, exponent) product of the
+// pivots in double, renormalised every update (a relative rounding per pivot, so the log taken
+// once at the end is off by about 1e-16 per pivot whatever the sum's size; a log per update
+// would add a rounding of the running sum each time, and ~25 VALU operations).  Branch-free and
+// the same code on every lane: a lane without a chain accumulates what nobody reads, and an aw
+// lane's inert third state, whose innovation is exactly 0 and whose pivot is exactly 1 + 1, adds
+// 0 to the NIS and 1 to the exponent per IMU update, which the final log takes back (exactly).
+struct ScoreAcc {
+    int32_t ngps = 0;               // applied GPS updates (the same in every lane of a group)
+    double nis[2] = {0.0, 0.0};     // this chain's sum of w_a^2 / d_a: GPS, IMU
+    double ldm[2] = {1.0, 1.0};     // this chain's pivot product, mantissa ...
+    int32_t lde[2] = {0, 0};        // ... and binary exponent
+    int32_t npos = 0;               // events scored against the track
+    double sse = 0.0;               // this axis' sum of (x - track)^2
+
+    // one applied update of this lane's chain
+    template <typename T, int M>
+    __device__ __forceinline__ void add(int kind, const Innov<T, M>& in) {
+        double m = ldm[kind];
+#pragma unroll
+        for (int a = 0; a < M; ++a) m *= double(in.d[a]);
+        nis[kind] += double(in.nis);
+        ldm[kind] = m;
+        renorm(ldm[kind], lde[kind]);
+    }
+};
+
 // Column f of a parameter sweep's constants table [2 N + NP][B] (SweepArgs::consts)
 struct ConstsColumn {
     const double* table;
@@ -851,9 +886,11 @@ struct ChainLane {
     // the aw lane's inert-state reset, and NaN poisoning of the whole group when any of its chains
     // failed (st then kNotSpd).  Returns whether the update was applied; every lane of the group
     // must call it together (the gate and the poisoning exchange over the group).
-    template <int NL>
+    // SCORE (a scored sweep): an applied update also adds its chain's innovation statistics to *sc
+    // (sel_update_nv's INNOV: the y, L and pivots of the update that runs anyway).
+    template <int NL, bool SCORE = false>
     __device__ __forceinline__ bool event(int type, T dt, T va, T vb, bool gated, const GateBand<T>& gate, T thr,
-                                          T (&x)[NL][3], T (&P)[6], int32_t& st) const {
+                                          T (&x)[NL][3], T (&P)[6], int32_t& st, ScoreAcc* sc = nullptr) const {
         if (type == 255) return false;
         // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
         const T c02 = pva ? T(0.5) * dt * dt : T(0);
@@ -891,8 +928,16 @@ struct ChainLane {
 #pragma unroll
                     for (int v = 0; v < NL; ++v) zb[v][0] = va;
                     const T R[1] = {Rgps};
-                    ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
+                    if constexpr (SCORE) {
+                        Innov<T, 1> inn;
+                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR, true>(
+                            x, P, zb, R, &inn);
+                        sc->add(0, inn);
+                    } else {
+                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
+                    }
                 }
+                if constexpr (SCORE) sc->ngps += 1;
             } else {
                 T zb[NL][3];
 #pragma unroll
@@ -903,7 +948,14 @@ struct ChainLane {
                     zb[v][1] = pva ? V : vb;
                     zb[v][2] = pva ? vb : T(0);
                 }
-                ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
+                if constexpr (SCORE) {
+                    Innov<T, 3> inn;
+                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR, true>(
+                        x, P, zb, Rimu, &inn);
+                    sc->add(1, inn);
+                } else {
+                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
+                }
                 if (!pva) {  // reset the inert state
 #pragma unroll
                     for (int v = 0; v < NL; ++v) x[v][2] = T(0);
@@ -935,10 +987,10 @@ struct ChainLane {
 // (profiles/r01_ab/chain_depth_inproc.json), so that default stays at 2.  Stream mode gathers
 // each filter's events from its own part of the stream (a cache line per 1.8 events, lines differ
 // per filter), so its loads see HBM latency: a deeper ring.
-template <int D, typename T, class Load, class Step>
+template <int D, typename T, class In = ChainIn<T>, class Load, class Step>
 __device__ __forceinline__ void ring_run(int n, Load&& load, Step&& step) {
     if (n <= 0) return;
-    ChainIn<T> buf[D];
+    In buf[D];
 #pragma unroll
     for (int j = 0; j < D - 1; ++j) load(j, buf[j]);
     __builtin_amdgcn_s_waitcnt(0);
@@ -1262,6 +1314,15 @@ __global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
 // instead of the literals or the handle's scalars, once, beside the threshold and before the
 // ring's prologue, whose drain covers those loads too; a.thresholds may be null (every group
 // -inf).  Everything after set-up is the sweep's: the ring, ChainLane::event, the records.
+//
+// SCORE (kf_run_sweep_scores; PARAMS only): the run ranked where it runs.  Each lane keeps a
+// ScoreAcc for its own chain, fed in event order: an applied update adds the NIS terms and the
+// pivots that sel_update_nv's INNOV hands out of the update itself, and after every event a pva
+// lane adds its axis' squared distance to the track row, which came through the ring with the
+// event's inputs (NP more loads per event: the compiler counts the ring's in-loop vmcnt waits per
+// instantiation, and the prologue's drain is a full one).  No atomics: after the last event one
+// group_sum per row, and lane 0 stores the eight rows.  The filter's own arithmetic, records and
+// checkpoints are the PARAMS kernel's.
 // ------------------------------------------------------------------------------------
 #ifndef KF_SWEEP_DEPTH
 #define KF_SWEEP_DEPTH 4
@@ -1276,9 +1337,10 @@ __device__ __forceinline__ auto sweep_consts(const SweepArgs& a, int64_t f) {
     else return a.kc;
 }
 
-template <typename T, class M, bool CUSTOM, bool TAILS = false, bool PARAMS = false>
+template <typename T, class M, bool CUSTOM, bool TAILS = false, bool PARAMS = false, bool SCORE = false>
 __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs a) {
     static_assert(!PARAMS || (!TAILS && !CUSTOM), "per-filter constants: the plain sweep, in place of the handle's");
+    static_assert(!SCORE || PARAMS, "scores: the parameter sweep's (track and scores share the tails' slots)");
     static_assert(consts_rows(M::N) == 2 * M::N + M::NP, "the table's rows: q, r_imu, r_gps");
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
     const int64_t f = g / kGroup;
@@ -1353,18 +1415,49 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
     const auto r_pay = bytes_rsrc(a.payload, S * 9u * uint32_t(sizeof(T)));
     // stream event ue's inputs; dead = ~0u drops the loads (offset 2^32 - 1 lies past every byte
     // range, the 4 GiB payload's too)
-    auto load = [&](uint32_t ue, uint32_t dead, ChainIn<T>& in) {
+    // SCORE: track row ue rides in the ring with the event's other inputs, the ring's last loads:
+    // a pva lane loads the columns the model reads, its own first (a null track: a zero-length
+    // range, loads nothing, scores nothing); the other lanes' loads are dropped (~0u lies past
+    // every byte range, 24 T < 2^32)
+    // (everything of SCORE sits under if constexpr or in a type that is empty without it: the
+    // other instantiations must stay the instruction streams they were)
+    using In = std::conditional_t<SCORE, ChainInScored<T>, ChainIn<T>>;
+    struct NoScore {};
+    std::conditional_t<SCORE, ScoreAcc, NoScore> sc;
+    auto load = [&](uint32_t ue, uint32_t dead, In& in) {
         in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue | dead, 0, 0));
         in.dt = ldv(r_dt, (ue * 8u) | dead, 0.0);
         in.va = ldv(r_pay, ((ue * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T))) | dead, T(0));
         in.vb = ldv(r_pay, ((ue * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T))) | dead, T(0));
+        if constexpr (SCORE) {
+            const auto r_trk = bytes_rsrc(a.track, S * 24u);
+            const uint32_t m_trk = L.pva ? 0u : ~0u;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                in.track[k] = k < M::NP ? ldv(r_trk, (ue * 24u + uint32_t((L.ca + k) % M::NP) * 8u) | m_trk | dead, 0.0)
+                                        : 0.0;
+        }
     };
     int ck_left = TAILS ? 0 : a.ckpt_every;  // events until the next checkpoint (wave-uniform)
     int ck_row = 0;
-    auto step = [&](int t, const ChainIn<T>& in) {
+    auto step = [&](int t, const In& in) {
         // every lane of the wave loaded the same type and dt: scalars (TAILS: the group's own)
         const int type = TAILS ? in.type : wave_uniform(in.type);
-        const bool applied = L.event(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st);
+        bool applied;
+        if constexpr (SCORE) {
+            applied = L.template event<1, true>(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st, &sc);
+            // the event's position against its track row, whatever its type: scored when every
+            // column the model reads is a number (a NaN in any of them: no reference here)
+            if (a.track != nullptr) {  // wave-uniform
+                const bool have = !(in.track[0] != in.track[0] || in.track[1] != in.track[1] ||
+                                    in.track[2] != in.track[2]);
+                const double e = have ? double(x[0][0]) - in.track[0] : 0.0;
+                sc.npos += have ? 1 : 0;
+                sc.sse = __builtin_fma(e, e, sc.sse);
+            }
+        } else {
+            applied = L.event(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st);
+        }
         nup += applied ? 1 : 0;
         // absent records: skipped by wave-uniform branches
         if (need_tr) stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, x[0][0]);
@@ -1400,7 +1493,7 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
             });
     } else {
         const int T_ = a.T;
-        ring_run<kSweepDepth, T>(T_, [&](int t, ChainIn<T>& in) { load(uint32_t(t < T_ ? t : T_ - 1), 0u, in); }, step);
+        ring_run<kSweepDepth, T, In>(T_, [&](int t, In& in) { load(uint32_t(t < T_ ? t : T_ - 1), 0u, in); }, step);
     }
     {
         const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
@@ -1415,6 +1508,32 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
         if (a.n_updated) {
             const auto rn = span_rsrc(a.n_updated, 0, uint32_t(a.B) * 4u, 1);
             __builtin_amdgcn_raw_buffer_store_b32(uint32_t(nup), rn, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
+        }
+    }
+    if constexpr (SCORE) {
+        // the eight rows of column f: each float row one group_sum of the chains' own sums (a GPS
+        // row: the pva chains'), the logs taken here, once; NaN where the filter failed.  Lane 0
+        // stores them (row r at r B 8 + f 8 of one span; 64 B < 2^31 by the state span's limit).
+        const bool pva = L.pva;
+        const double nan = quiet_nan<double>();
+        const bool bad = st != 0;
+        double row[kScoreRows];
+        const int32_t nimu = nup - sc.ngps;  // every applied update is a fix or an IMU event
+        row[kScoreGpsN] = double(sc.ngps);
+        row[kScoreGpsNis] = group_sum(pva ? sc.nis[0] : 0.0);
+        row[kScoreGpsLogdetS] = group_sum(pva ? log_mant(sc.ldm[0], sc.lde[0]) : 0.0);
+        row[kScoreImuN] = double(nimu);
+        row[kScoreImuNis] = group_sum(live ? sc.nis[1] : 0.0);
+        // an aw chain's S is 2 x 2: its inert third pivot, exactly 2 every update, out of the exponent
+        row[kScoreImuLogdetS] = group_sum(live ? log_mant(sc.ldm[1], sc.lde[1] - (pva ? 0 : nimu)) : 0.0);
+        row[kScorePosN] = double(sc.npos);
+        row[kScorePosSse] = group_sum(pva ? sc.sse : 0.0);
+        const auto rs = span_rsrc(a.scores, 0, uint32_t(a.B) * 8u, kScoreRows);
+#pragma unroll
+        for (int r = 0; r < kScoreRows; ++r) {
+            const bool count = r == kScoreGpsN || r == kScoreImuN || r == kScorePosN;
+            stv(rs, c == 0 ? (uint32_t(r) * uint32_t(a.B) + uint32_t(f)) * 8u : kDropOffset,
+                bad && !count ? nan : row[r]);
         }
     }
 }
@@ -4882,10 +5001,14 @@ hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
+hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream, bool scored) {
     if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || (!a.thresholds && !a.consts)) return hipErrorInvalidValue;
+    if (scored && (!a.consts || !a.scores)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    if (a.consts)
+    if (a.consts && scored)
+        KF_MODEL_DISPATCH(model, f64,
+                          ref_sweep_kernel<T, M, false, false, true, true><<<grid, kSweepBlock, 0, stream>>>(a));
+    else if (a.consts)
         KF_MODEL_DISPATCH(model, f64, ref_sweep_kernel<T, M, false, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
     else
         KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));

@@ -37,6 +37,15 @@ KF_INGEST_GPS_ALTITUDE = 1
 KF_DT_FULL = 0
 KF_DT_MONOTONE = 1
 KF_DT_RAW = 2
+KF_SCORE_GPS_N = 0
+KF_SCORE_GPS_NIS = 1
+KF_SCORE_GPS_LOGDET_S = 2
+KF_SCORE_IMU_N = 3
+KF_SCORE_IMU_NIS = 4
+KF_SCORE_IMU_LOGDET_S = 5
+KF_SCORE_POS_N = 6
+KF_SCORE_POS_SSE = 7
+KF_SCORE_ROWS = 8
 
 KF_OPT_PREDICT = 1
 KF_OPT_CV_KERNEL = 2
@@ -117,6 +126,7 @@ SIGNATURES = {
     'kf_run_stream': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'kf_run_sweep': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_run_sweep_params': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'kf_run_sweep_scores': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_consts_rows': (_i, [_i, ctypes.POINTER(_i)]),
     'kf_run_tails': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
     'kf_stream_check': (_i, [_vp, _vp, _vp]),
@@ -191,7 +201,11 @@ def lib():
     except OSError as e:  # pragma: no cover - depends on the host
         raise KFError(KF_ENODEV, f'cannot load {LIB_PATH}: {e}') from e
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(handle, name)
+        fn = getattr(handle, name, None)
+        if fn is None:
+            if os.environ.get('KFMI_ALLOW_FOREIGN_LIB') == '1':
+                continue  # another revision's build (A/B only) may predate an entry point
+            raise KFError(KF_ENODEV, f'{LIB_PATH} does not export {name}: rebuild (make -C sensorfusion-kalmanfilter_amd)')
         fn.restype = res
         fn.argtypes = args
     if os.environ.get('KFMI_ALLOW_FOREIGN_LIB') != '1':

@@ -7,6 +7,7 @@ allocator / stream provider here); all arithmetic happens in the HIP kernels.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 
@@ -80,6 +81,28 @@ def consts_table(model, sets):
     for f, c in enumerate(sets):
         tab[:, f] = np.concatenate([c.q, c.r_imu, c.r_gps])
     return tab
+
+
+# rows of run_sweep_scores' [8, B] table (kf.h's KF_SCORE_*)
+SCORE_ROWS = {'gps_n': _lib.KF_SCORE_GPS_N, 'gps_nis': _lib.KF_SCORE_GPS_NIS,
+              'gps_logdet_s': _lib.KF_SCORE_GPS_LOGDET_S, 'imu_n': _lib.KF_SCORE_IMU_N,
+              'imu_nis': _lib.KF_SCORE_IMU_NIS, 'imu_logdet_s': _lib.KF_SCORE_IMU_LOGDET_S,
+              'pos_n': _lib.KF_SCORE_POS_N, 'pos_sse': _lib.KF_SCORE_POS_SSE}
+assert len(SCORE_ROWS) == _lib.KF_SCORE_ROWS
+
+SweepScores = collections.namedtuple('SweepScores', 'scores n_updated traj logdet updated ckpt_x ckpt_P')
+
+
+def innovation_nll(scores, model, sensor):
+    """The Gaussian innovation negative log-likelihood per filter from run_sweep_scores' table
+    ([8, B], a tensor or an array): -sum over the sensor's applied updates of log N(y; 0, S) =
+    0.5 (NIS + logdet_S + n m log 2 pi), m the measurement's length (GPS 3 | 2, IMU 15 | 8 for
+    'ref15' | 'ref8').  ``sensor``: 'gps' | 'imu'."""
+    if model not in REF_MODELS or sensor not in ('gps', 'imu'):
+        raise ValueError(f'innovation_nll: model {model!r}, sensor {sensor!r}')
+    m = {'ref15': (3, 15), 'ref8': (2, 8)}[model][sensor == 'imu']
+    n, nis, ld = (scores[SCORE_ROWS[f'{sensor}_{k}']] for k in ('n', 'nis', 'logdet_s'))
+    return 0.5 * (nis + ld + n * (m * math.log(2.0 * math.pi)))
 
 
 def device_count():
@@ -451,6 +474,28 @@ class BatchedKF:
         constants (its P0 is the caller's set_state), and ``thresholds`` may be None: every filter
         always updates.  A table of another dtype or shape and a list of another length are
         KFError(KF_EINVAL)."""
+        return self._sweep(etype, dt, payload, thresholds, traj, logdet, updated, counts, checkpoint_every, consts)[:6]
+
+    def run_sweep_scores(self, etype, dt, payload, consts, thresholds=None, track=None, traj=False, logdet=False,
+                         updated=False, checkpoint_every=0):
+        """run_sweep(consts=...) that also scores every filter on the device (kf_run_sweep_scores):
+        the same launch, the same records, counts, checkpoints, end state and status bit for bit,
+        plus ``scores``, a [8, B] float64 tensor (rows: SCORE_ROWS) of the applied updates' count,
+        NIS y^T S^-1 y and log det S per sensor, and the count and sum of squared position errors
+        against ``track`` ([T, 3] float64, row t the reference position at event t, NaN rows not
+        scored; None: rows 6 and 7 stay 0).  ``consts`` is mandatory (a table or a list of
+        ModelConsts, as in run_sweep).  A filter that failed has NaN in its float rows.  Returns
+        SweepScores(scores, n_updated, traj, logdet, updated, ckpt_x, ckpt_P), None where not asked
+        for."""
+        if consts is None:
+            raise KFError(_lib.KF_EINVAL, 'run_sweep_scores: consts is mandatory (a table with equal columns scores '
+                                          'a threshold sweep under one set)')
+        tr, ld, up, nu, cx, cP, sc = self._sweep(etype, dt, payload, thresholds, traj, logdet, updated, True,
+                                                 checkpoint_every, consts, scored=True, track=track)
+        return SweepScores(sc, nu, tr, ld, up, cx, cP)
+
+    def _sweep(self, etype, dt, payload, thresholds, traj, logdet, updated, counts, checkpoint_every, consts,
+               scored=False, track=None):
         if self.model not in REF_MODELS:
             raise ValueError('run_sweep needs a ref15 or ref8 handle')
         tab = None
@@ -477,6 +522,14 @@ class BatchedKF:
         every = int(checkpoint_every)
         if every < 0:
             raise ValueError('checkpoint_every must be >= 0')
+        trk = None
+        if track is not None:
+            if isinstance(track, np.ndarray):
+                track = torch.from_numpy(np.ascontiguousarray(track))
+            if not torch.is_tensor(track) or track.dtype != torch.float64 or tuple(track.shape) != (T, 3):
+                raise KFError(_lib.KF_EINVAL, f'track: expected a float64 [T, 3] = {(T, 3)} array, got '
+                                              f'{getattr(track, "dtype", type(track))} {tuple(getattr(track, "shape", ()))}')
+            trk = self._dev(track, (T, 3), 'track', torch.float64)
         et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
         dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
         pay = self._dev(payload.reshape(T, 9), (T, 9), 'payload')
@@ -485,17 +538,21 @@ class BatchedKF:
         ld = self.empty(T, self.batch) if logdet else None
         up = torch.empty(T, self.batch, dtype=torch.uint8, device=self.device) if updated else None
         nu = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if counts else None
+        sc = torch.empty(len(SCORE_ROWS), self.batch, dtype=torch.float64, device=self.device) if scored else None
         C = T // every if every > 0 else 0
         cx = self.empty(C, self.n, self.batch) if every > 0 else None
         cP = self.empty(C, self.ntri, self.batch) if every > 0 else None
         ck = (every, _ptr(cx) if C else None, _ptr(cP) if C else None, self._stream())
-        if tab is None:
+        if scored:
+            check(_lib.lib().kf_run_sweep_scores(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tab),
+                                                 _ptr(trk), _ptr(sc), _ptr(tr), _ptr(ld), _ptr(up), _ptr(nu), *ck))
+        elif tab is None:
             check(_lib.lib().kf_run_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tr),
                                           _ptr(ld), _ptr(up), _ptr(nu), *ck))
         else:
             check(_lib.lib().kf_run_sweep_params(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tab),
                                                  _ptr(tr), _ptr(ld), _ptr(up), _ptr(nu), *ck))
-        return tr, ld, up, nu, cx, cP
+        return tr, ld, up, nu, cx, cP, sc
 
     def run_tails(self, etype, dt, payload, lo, hi, thresholds, src_x=None, src_P=None, src_row=None, src_col=None,
                   counts=False):

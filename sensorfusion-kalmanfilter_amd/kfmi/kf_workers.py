@@ -480,16 +480,17 @@ class KF_SensorFusion:
                                                   checkpoint_every=checkpoint_every)
 
     def run_parameter_sweep(self, consts_list, thresholds=None, start_idx=None, end_idx=None, initial_pt=None,
-                            initial_state=None, records=True, checkpoint_every=4096):
+                            initial_state=None, records=True, checkpoint_every=4096, track=None, scores=False):
         """run_adaptive_threshold_kalman_filter under every constant set of ``consts_list``
         (ref15.ModelConsts, e.g. ModelConsts.from_matrices of replaced getters) in one launch
         (ref15.ParameterSweep): filter i runs under consts_list[i] and thresholds[i] (None: no
         gate); .result(i) is that run's return value, .warm_start(i, end_idx) its prefix's
-        (states[-1], P, previous_time).  This object's own getters are not read."""
+        (states[-1], P, previous_time).  This object's own getters are not read.  scores=True: the
+        sets are ranked in the same launch (.scores, .best; ``track``: None = the stream's fixes)."""
         return ref15.run_parameter_sweep(self.indexed_sensor_data, consts_list, thresholds, start_idx=start_idx,
                                          end_idx=end_idx, initial_pt=initial_pt, initial_state=initial_state,
                                          dtype=self.dtype, device=self.device, records=records,
-                                         checkpoint_every=checkpoint_every)
+                                         checkpoint_every=checkpoint_every, track=track, scores=scores)
 
     def run_no_update_kalman_filter(self, start_idx=None, end_idx=None, R_threshold=None, initial_pt=None,
                                     initial_state=None, print_output=False):

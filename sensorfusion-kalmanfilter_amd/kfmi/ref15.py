@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import BatchedKF, consts_table
+from .engine import BatchedKF, SCORE_ROWS, consts_table, innovation_nll
 
 GPS, IMU, PREDICT, NONE = _lib.KF_EVENT_GPS, _lib.KF_EVENT_IMU, _lib.KF_EVENT_PREDICT, _lib.KF_EVENT_NONE
 
@@ -597,10 +597,11 @@ class AdaptiveSweep:
     warm_start(index[w], end_idxs[w]), every tail in one launch (kf_run_tails)."""
 
     def __init__(self, events, thresholds, start_idx=None, end_idx=None, initial_pt=None, initial_state=None,
-                 dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096):
+                 dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096, scores=False, track=None):
         from .ingest import events_dt
         self.thresholds = np.array(thresholds, dtype=np.float64).reshape(-1)
         self.dtype, self.consts, self.records = dtype, consts, bool(records)
+        self.scored, self.scores = bool(scores), None
         self.every = int(checkpoint_every)
         self.n_updates = np.zeros(len(self.thresholds), np.int64)
         self.empty = True  # a cold window without a fix: the driver returns None
@@ -686,12 +687,36 @@ class AdaptiveSweep:
         self._kf1 = None
         if self.empty:
             return
+        if self.scored:
+            # the scored launch takes a table: this sweep's one constant set in every column
+            if self._table is None:
+                one = consts if consts is not None else ModelConsts('ref15')
+                self._table = torch.from_numpy(consts_table('ref15', [one] * B)).to(dev)
+            # the track at the entries' times (entry 0 is states[0], at the start time); a skipped
+            # dt < 0 entry is no state of the driver's: no reference there
+            if track is None and getattr(events, 'h', None) is None and ds is None:
+                # a plain event list's own fixes, at the events' own times
+                fixes = [(t, sd) for _, stype, t, sd in events if stype == 'GPS']
+                track = (np.array([t for t, _ in fixes], np.float64),
+                         np.array([[sd['easting'], sd['northing'], sd['altitude']] for _, sd in fixes], np.float64))
+            tt, tp = _track_of(events, track)
+            rows = track_positions(tt, tp, self._t)
+            rows[~self._keep] = np.nan
+            self._track = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
         kf = BatchedKF('ref15', B, dtype, device=dev.index or 0, params=_params(consts))
         try:
             kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
-            (self._traj, self._ld, self._up, nu, self._cx, self._cP) = kf.run_sweep(
-                self._et, self._dt, self._pay, torch.from_numpy(self.thresholds), traj=self.records,
-                logdet=self.records, updated=self.records, checkpoint_every=self.every, consts=self._table)
+            if self.scored:
+                r = kf.run_sweep_scores(self._et, self._dt, self._pay, self._table, torch.from_numpy(self.thresholds),
+                                        track=self._track, traj=self.records, logdet=self.records,
+                                        updated=self.records, checkpoint_every=self.every)
+                self._traj, self._ld, self._up, nu, self._cx, self._cP = (r.traj, r.logdet, r.updated, r.n_updated,
+                                                                          r.ckpt_x, r.ckpt_P)
+                self.scores = _scores_dict(r.scores.cpu().numpy())
+            else:
+                (self._traj, self._ld, self._up, nu, self._cx, self._cP) = kf.run_sweep(
+                    self._et, self._dt, self._pay, torch.from_numpy(self.thresholds), traj=self.records,
+                    logdet=self.records, updated=self.records, checkpoint_every=self.every, consts=self._table)
             self._x, self._Pb = kf.state()
             self._status = kf.status()
             self.n_updates = nu.cpu().numpy().astype(np.int64)
@@ -711,6 +736,15 @@ class AdaptiveSweep:
             self.close()
         except Exception:
             pass
+
+    def best(self, by='gps_nll'):
+        """Index of the filter with the smallest finite ``scores[by]`` (needs scores=True)."""
+        if self.scores is None:
+            raise ValueError('best needs scores=True and a window that ran')
+        v = np.asarray(self.scores[by], np.float64)
+        if not np.isfinite(v).any():
+            raise ValueError(f'best: no finite {by}')
+        return int(np.argmin(np.where(np.isfinite(v), v, np.inf)))
 
     def result(self, i):
         """(states, logdets, P, previous_time, measurement_times) of
@@ -805,6 +839,17 @@ class AdaptiveSweep:
         return out
 
 
+def _scores_dict(table):
+    """run_sweep_scores' [8, B] table as the sweeps' ``scores``: the counts, sums and innovation
+    negative log-likelihoods per sensor, pos_n and pos_rmse = sqrt(pos_sse / pos_n)."""
+    d = {k: table[r].copy() for k, r in SCORE_ROWS.items() if k != 'pos_sse'}
+    for sensor in ('gps', 'imu'):
+        d[f'{sensor}_nll'] = innovation_nll(table, 'ref15', sensor)
+    n = table[SCORE_ROWS['pos_n']]
+    d['pos_rmse'] = np.sqrt(np.where(n > 0, table[SCORE_ROWS['pos_sse']], np.nan) / np.where(n > 0, n, 1.0))
+    return d
+
+
 def run_adaptive_threshold_sweep(events, thresholds, **kw):
     """The AdaptiveSweep of ``events`` under ``thresholds`` (its keyword arguments)."""
     return AdaptiveSweep(events, thresholds, **kw)
@@ -823,10 +868,20 @@ class ParameterSweep(AdaptiveSweep):
     consts=consts_list[i]) returns.  ``warm_start(i, end_idx)``: its prefix's (states[-1], P,
     previous_time), the tail past the checkpoint run as a one-filter parameter sweep with set i's
     column, so it rounds as the sweep did.  ``warm_starts`` is the list of those (kf_run_tails
-    has no per-filter constants: one launch per tail)."""
+    has no per-filter constants: one launch per tail).
+
+    ``scores=True`` makes the one launch kf_run_sweep_scores (AdaptiveSweep takes it too, with its
+    one constant set in every column), so the grid is ranked without records (``records=False``
+    loses nothing of the ranking): ``.scores`` is a dict of NumPy [B] arrays gps_n, gps_nis,
+    gps_logdet_s, gps_nll, the same four for imu, pos_n and pos_rmse, the position error against
+    ``track`` (anything _track_of takes; None: the stream's own fixes) interpolated at the entries'
+    times with track_positions as calculate_accuracy_metrics does (kf_workers.py:1162-1216); the
+    leading NONE entry is scored (it is states[0]), a skipped dt < 0 entry is not.  ``.best(by)``:
+    the index of the smallest finite scores[by]."""
 
     def __init__(self, events, consts_list, thresholds=None, start_idx=None, end_idx=None, initial_pt=None,
-                 initial_state=None, dtype='f64', device=0, records=True, checkpoint_every=4096):
+                 initial_state=None, dtype='f64', device=0, records=True, checkpoint_every=4096, track=None,
+                 scores=False):
         self._sets = list(consts_list)
         if thresholds is None:
             thresholds = np.full(len(self._sets), -np.inf)
@@ -837,7 +892,7 @@ class ParameterSweep(AdaptiveSweep):
             if not isinstance(c, ModelConsts) or c.model != 'ref15':
                 raise ValueError('ParameterSweep: consts_list holds ModelConsts(\'ref15\', ...)')
         super().__init__(events, thresholds, start_idx, end_idx, initial_pt, initial_state, dtype, device, None,
-                         records, checkpoint_every)
+                         records, checkpoint_every, scores, track)
         self.consts_list = self._sets
 
     def warm_starts(self, index, end_idxs):
