@@ -487,6 +487,47 @@ int kf_run_sweep_scores(kf_batch* handle, int T, const uint8_t* etype, const dou
                         void* traj, void* logdet, uint8_t* updated, int32_t* n_updated,
                         int ckpt_every, void* ckpt_x, void* ckpt_P, void* stream);
 
+/* Fixed-interval (Rauch-Tung-Striebel) smoother over a sweep's filtered record: what each of the
+ * B filters could know about every event with the whole stream in hand.  KF_MODEL_REF15 /
+ * KF_MODEL_REF8, f64 handles only (an f32 handle or another model: KF_EINVAL).  etype, dt and
+ * consts are kf_run_sweep_params' (device [T], [T], [R][B] or NULL = the handle's constants; only
+ * the Q rates are read).  filt_x [T][n][B] / filt_P [T][27|15][B] are the ckpt_x / ckpt_P of a
+ * sweep with ckpt_every = 1: row t the filter after event t.  Any record in that layout is
+ * accepted; the call does not require that a sweep produced it.  The handle gives the model and
+ * the constants only: its state and status are neither read nor written.
+ *
+ * Row T - 1 of the result is the filtered row.  For t = T - 2 .. 0, with (x_f, P_f) = row t:
+ *   etype[t + 1] == KF_EVENT_NONE: the forward step changed nothing, row t is row t + 1;
+ *   otherwise   x_p = F x_f,  P_p = F P_f F^T + Q dt[t + 1]   (the event step's own predict)
+ *               C = (P_f F^T) P_p^-1
+ *               x_s[t] = x_f + C (x_s[t + 1] - x_p)
+ *               P_s[t] = P_f + C (P_s[t + 1] - P_p) C^T
+ * whether event t + 1 was a fix, an IMU event or KF_EVENT_PREDICT, applied or gated away: its
+ * update is already in x_s[t + 1].  P is block-diagonal over the axis chains and F acts within a
+ * chain, so C is block-diagonal too and every chain is smoothed on its own, with the gain from an
+ * LDL^T of P_p whose pivots are divided by exactly (the updates' one-Newton reciprocal is not
+ * accurate enough here: P_f - C P_p C^T cancels); P_s is formed once per packed entry, so it is
+ * symmetric.
+ *
+ * Outputs, device, each may be NULL: sm_x [T][n][B], sm_P [T][27|15][B] (block-packed), sm_traj
+ * [T][6|3][B] (kf_run_sweep's traj), sm_logdet [T][B] (log det P_s), sm_status [B] int32.
+ * sm_x == filt_x and / or sm_P == filt_P exactly is legal (every row is read before it is
+ * written) and halves the memory of a long log; any other overlap is undefined and not checked.
+ * A non-positive pivot of P_p or a NaN in a row of the record fails that filter alone: its rows
+ * from that t down to 0 are NaN and its sm_status is KF_ENOTSPD; its rows above, and its
+ * neighbours, are untouched.  T = 0 is KF_OK and writes nothing; T = 1 copies the filtered row.
+ *
+ * Bit for bit: row T - 1 is the filtered row; row t is row t + 1 wherever etype[t + 1] is NONE;
+ * and a filter's rows do not depend on B, on its place in its wave, on which outputs are NULL or
+ * on running in place.  Memory: the filtered record is 336 B (KF_MODEL_REF8: 184 B) per event and
+ * filter.  Asynchronous on `stream`, capturable; allocates nothing.  Limits (KF_EINVAL before
+ * anything is queued): 27 B 8 < 2 GiB, 8 T < 4 GiB, the table R B 8 < 2 GiB; NULL filt_x, filt_P,
+ * etype or dt with T > 0.  The reference has no smoother; this is the backward half of the
+ * textbook fixed-interval smoother over kf_workers.py:959-1058's forward run. */
+int kf_smooth_sweep(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const double* consts,
+                    const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj,
+                    void* sm_logdet, int32_t* sm_status, void* stream);
+
 /* Rows of kf_run_sweep_params' consts table for `model`: 33 for KF_MODEL_REF15 (ref_q 15, ref_r_imu
  * 15, ref_r_gps 3), 18 for KF_MODEL_REF8 (8, 8, 2).  KF_EINVAL for any other model or NULL rows. */
 int kf_consts_rows(int model, int* rows);

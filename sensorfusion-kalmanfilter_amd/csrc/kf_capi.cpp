@@ -1106,6 +1106,44 @@ int kf_run_sweep_scores(kf_batch* h, int T, const uint8_t* etype, const double* 
                           n_updated, ckpt_every, ckpt_x, ckpt_P, stream, track, scores);
 }
 
+int kf_smooth_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const double* consts,
+                    const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj, void* sm_logdet,
+                    int32_t* sm_status, void* stream) {
+    const char* fn = "kf_smooth_sweep";
+    if (int rc = check_handle(h)) return rc;
+    if (!is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle", fn);
+    if (h->dtype != KF_F64) return fail(KF_EINVAL, "%s: needs an f64 handle (the f32 smoother is not built)", fn);
+    if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
+    if (T == 0 || h->B == 0) return KF_OK;
+    if (!etype || !dt || !filt_x || !filt_P) return fail(KF_EINVAL, "%s: null etype/dt/filt_x/filt_P", fn);
+    // the kernel's descriptors: etype and dt by byte range (32-bit), a record row as one span whose
+    // offsets keep bit 31 free for dropped lanes
+    if (uint64_t(T) * 8u >= (uint64_t(1) << 32))
+        return fail(KF_EINVAL, "%s: T = %d events exceed the 4 GiB dt descriptor (8 T)", fn, T);
+    if (uint64_t(h->B) * 27u * 8u >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB row span (27 B 8)", fn, (long long)h->B);
+    const int model = h->model == KF_MODEL_REF15 ? 15 : 8;
+    if (consts && uint64_t(kfmi::consts_rows(model)) * uint64_t(h->B) * 8u >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB constants table (%d B 8)", fn, (long long)h->B,
+                    kfmi::consts_rows(model));
+    kfmi::SmoothArgs a{};
+    a.B = h->B;
+    a.T = T;
+    a.etype = etype;
+    a.dt = dt;
+    a.filt_x = filt_x;
+    a.filt_P = filt_P;
+    a.sm_x = sm_x;
+    a.sm_P = sm_P;
+    a.sm_traj = sm_traj;
+    a.sm_logdet = sm_logdet;
+    a.sm_status = sm_status;
+    a.kc = h->kc;
+    a.consts = consts;
+    hipError_t e = kfmi::launch_ref_smooth(model, a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
 int kf_consts_rows(int model, int* rows) {
     if (!is_ref(model))
         return fail(KF_EINVAL, "kf_consts_rows: model %d has no per-filter constants (KF_MODEL_REF15 or KF_MODEL_REF8)",

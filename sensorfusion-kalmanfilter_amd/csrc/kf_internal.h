@@ -175,6 +175,25 @@ enum : int {
 // rows of SweepArgs::consts: q [N], r_imu [N], r_gps [NP]
 constexpr int consts_rows(int model) { return model == 15 ? 33 : 18; }
 
+// RTS smoother over a sweep's filtered record (kf_smooth_sweep; ref_smooth_kernel): the backward
+// pass over filt_x / filt_P, the ckpt_x / ckpt_P of a sweep with ckpt_every = 1, under the Q rates
+// of the handle (kc) or of column f of consts.  Every output may be nullptr.
+struct SmoothArgs {
+    int64_t B;
+    int T;
+    const uint8_t* etype;    // [T]
+    const double* dt;        // [T]
+    const void* filt_x;      // [T][N][B]
+    const void* filt_P;      // [T][NBLK][B]
+    void* sm_x;              // [T][N][B]; may be filt_x
+    void* sm_P;              // [T][NBLK][B]; may be filt_P
+    void* sm_traj;           // [T][NTRAJ][B]
+    void* sm_logdet;         // [T][B]
+    int32_t* sm_status;      // [B]
+    const RefConsts* kc;     // the handle's own noise constants (device), or nullptr: the reference's
+    const double* consts;    // [consts_rows][B] or nullptr: kc
+};
+
 // Time-parallel run of one filter over a long event stream (kf_run_stream): the state banks of
 // the three chunk passes and the check.  Bank layouts are the handle's ([N][B], [NBLK][B]).
 struct StreamCheck {
@@ -508,6 +527,8 @@ hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t 
 hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream, bool scored = false);
 // ragged tails of one stream (ref_sweep_kernel's TAILS instantiations; a.tails set, a.T >= 0)
 hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream);
+// the RTS backward pass (f64 only)
+hipError_t launch_ref_smooth(int model, const SmoothArgs& a, hipStream_t stream);
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream);
 hipError_t launch_ref15_combos(bool f64, const Ref15ComboArgs& a, hipStream_t stream);
 // child_major: one wave per (parent block, child event) instead of one lane per parent

@@ -881,6 +881,40 @@ struct ChainLane {
     // P[k] where the lane holds no row k: the identity (an aw lane's inert state has variance 1)
     static __device__ __forceinline__ T unit(int k) { return T(k == 0 || k == 3 || k == 5 ? 1 : 0); }
 
+    // event's predict, line for line, for ref_smooth_kernel: x = F x for the NL states, P = F P F^T
+    // + Q dt, F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane), the same
+    // operations in the same order, so its P is event's P_pred bit for bit.  FP leaves with F P of
+    // the covariance that came in (the smoother gain reads it).  event keeps its own copy of these
+    // lines: calling this member from it compiled every chain-layout kernel to another instruction
+    // stream (profiles/rts_smoother/isa_compare_predict_member.log).  Change both together.
+    template <int NL>
+    __device__ __forceinline__ void predict(T dt, T (&x)[NL][3], T (&P)[6], T (&FP)[3][3]) const {
+        const T c02 = pva ? T(0.5) * dt * dt : T(0);
+        const T c12 = pva ? dt : T(0);
+#pragma unroll
+        for (int v = 0; v < NL; ++v) {
+            const T xn0 = fmaT(c02, x[v][2], fmaT(dt, x[v][1], x[v][0]));
+            const T xn1 = fmaT(c12, x[v][2], x[v][1]);
+            x[v][0] = xn0;
+            x[v][1] = xn1;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
+            FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
+            FP[2][j] = P[tri<3>(2, j)];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                T s = FP[i][j];
+                if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
+                if (j == 1) s = fmaT(FP[i][2], c12, s);
+                P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
+            }
+    }
+
     // One event on this lane's chain, for NL states that share the covariance: predict, the
     // adaptive gate (gated: against thr, through the group's GateBand), the GPS / IMU update,
     // the aw lane's inert-state reset, and NaN poisoning of the whole group when any of its chains
@@ -1535,6 +1569,209 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
             stv(rs, c == 0 ? (uint32_t(r) * uint32_t(a.B) + uint32_t(f)) * 8u : kDropOffset,
                 bad && !count ? nan : row[r]);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// Fixed-interval (Rauch-Tung-Striebel) smoother over a sweep's filtered record (kf_smooth_sweep):
+// the backward pass over ckpt_x / ckpt_P of a sweep with ckpt_every = 1, in the sweep's layout (8
+// lanes per filter, lane c on axis chain c, one wave per workgroup).  P is block-diagonal over the
+// chains and F acts within a chain, so the smoother gain is block-diagonal too: each lane smooths
+// its own 3 x 3 block and holds the smoothed (x, P) of event t + 1 in registers, 3 + 6 values.
+// Row T - 1 is the filtered row.  For t = T - 2 .. 0, with (x_f, P_f) the filtered row t:
+//   etype[t + 1] == NONE: the forward step changed nothing, row t is row t + 1 (no arithmetic);
+//   otherwise  x_p = F x_f, P_p = F P_f F^T + Q dt[t + 1]   (ChainLane::predict, so P_p is the
+//                                                           forward run's own P_pred bit for bit)
+//              C = (P_f F^T) P_p^-1                         (in-lane LDL^T of P_p; its three pivots'
+//                                                           reciprocals are IEEE divisions, see there)
+//              x_s[t] = x_f + C (x_s[t + 1] - x_p)
+//              P_s[t] = P_f + C (P_s[t + 1] - P_p) C^T      (once per packed entry i <= j)
+// whatever the event at t + 1 was: its update is already in x_s[t + 1].  A lane without a chain
+// runs the same code on the unit block; an aw lane's inert third state stays (0, 1).
+// The inputs come backwards through ring_run (step s is t = T - 2 - s): etype and dt of t + 1 by
+// byte-range descriptors, the lane's 3 + 6 values of row t by a span descriptor with a 64-bit base
+// per event.  A row is loaded kSmoothDepth - 1 steps before the step that may overwrite it, so
+// sm_x == filt_x and sm_P == filt_P are legal.  No atomics, no LDS, no workspace.
+// A non-positive pivot of P_p or a NaN in a loaded row poisons the filter's group from that t down
+// to 0 (NaN rows, KF_ENOTSPD in sm_status); the rows above it are already stored.
+// ------------------------------------------------------------------------------------
+#ifndef KF_SMOOTH_DEPTH
+#define KF_SMOOTH_DEPTH KF_SWEEP_DEPTH
+#endif
+constexpr int kSmoothDepth = KF_SMOOTH_DEPTH;  // input ring of ref_smooth_kernel
+
+// One backward step's inputs for one lane: the event after the row, and the lane's part of the row
+template <typename T>
+struct SmoothIn {
+    int type;
+    double dt;
+    T x[3], P[6];
+};
+
+template <bool PARAMS>
+__device__ __forceinline__ auto smooth_consts(const SmoothArgs& a, int64_t f) {
+    if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
+    else return a.kc;
+}
+
+template <typename T, class M, bool CUSTOM, bool PARAMS = false>
+__global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArgs a) {
+    static_assert(!PARAMS || !CUSTOM, "per-filter constants in place of the handle's");
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
+    const int64_t f = g / kGroup;
+    if (f >= a.B) return;  // whole groups leave together
+    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), smooth_consts<PARAMS>(a, f));
+    const int c = L.c;
+    const bool live = L.live;
+    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
+    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
+    uint32_t vx[3], vp[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vx[k] = L.xi[k] >= 0 ? uint32_t(L.xi[k]) * rb + off : kDropOffset;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vp[k] = L.pr[k] >= 0 ? uint32_t(L.pr[k]) * rb + off : kDropOffset;
+    const uint32_t v_tr = (L.xi[0] >= 0 && L.xi[0] < M::NTRAJ) ? uint32_t(L.xi[0]) * rb + off : kDropOffset;
+    const uint32_t v_ld = c == 0 ? off : kDropOffset;
+    const bool need_x = a.sm_x != nullptr, need_P = a.sm_P != nullptr;
+    const bool need_tr = a.sm_traj != nullptr, need_ld = a.sm_logdet != nullptr;
+
+    const int T_ = a.T;
+    const uint32_t S = uint32_t(T_);
+    const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
+    // row t of the filtered record: the lane's states and block rows (the rows it does not hold
+    // are dropped loads, 0, and the identity's entries)
+    auto load_row = [&](int t, T (&x)[3], T (&P)[6]) {
+        const auto rx = span_rsrc(a.filt_x, int64_t(t) * M::N, rb, M::N);
+        const auto rp = span_rsrc(a.filt_P, int64_t(t) * M::NBLK, rb, M::NBLK);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[k] = ldv(rx, vx[k], T(0));
+#pragma unroll
+        for (int k = 0; k < 6; ++k) P[k] = L.pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
+    };
+    auto is_nan_row = [&](const T (&x)[3], const T (&P)[6]) {
+        bool nan = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nan = nan || x[k] != x[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) nan = nan || P[k] != P[k];
+        return nan;
+    };
+    int32_t st = 0;
+    T xs[1][3], Ps[6];  // the smoothed row t + 1
+    auto poison = [&]() {
+        st = kNotSpd;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xs[0][k] = quiet_nan<T>();
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Ps[k] = quiet_nan<T>();
+    };
+    // absent outputs: skipped by wave-uniform branches
+    auto store_row = [&](int t) {
+        if (need_x) {
+            const auto rx = span_rsrc(a.sm_x, int64_t(t) * M::N, rb, M::N);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) stv(rx, vx[k], xs[0][k]);
+        }
+        if (need_P) {
+            const auto rp = span_rsrc(a.sm_P, int64_t(t) * M::NBLK, rb, M::NBLK);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) stv(rp, vp[k], Ps[k]);
+        }
+        if (need_tr) stv(span_rsrc(a.sm_traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, xs[0][0]);
+        if (need_ld) {
+            const T ld = group_sum(live ? chain_log_det(Ps) : T(0));
+            stv(span_rsrc(a.sm_logdet, t, rb, 1), v_ld, ld);
+        }
+    };
+
+    // row T - 1: the filtered row itself
+    load_row(T_ - 1, xs[0], Ps);
+    __builtin_amdgcn_s_waitcnt(0);
+    if (group_any(live && is_nan_row(xs[0], Ps))) poison();
+    store_row(T_ - 1);
+
+    const int n = T_ - 1;  // backward steps; step s is row t = T - 2 - s (past the end: row 0 again)
+    auto load = [&](int s, SmoothIn<T>& in) {
+        const int t = T_ - 2 - (s < n ? s : n - 1);
+        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, uint32_t(t + 1), 0, 0));
+        in.dt = ldv(r_dt, uint32_t(t + 1) * 8u, 0.0);
+        load_row(t, in.x, in.P);
+    };
+    auto step = [&](int s, const SmoothIn<T>& in) {
+        const int t = T_ - 2 - s;
+        const int type = wave_uniform(in.type);  // every lane loaded the same type and dt
+        bool bad = is_nan_row(in.x, in.P);
+        if (type != 255) {
+            const T dt = T(in.dt);
+            T xp[1][3] = {{in.x[0], in.x[1], in.x[2]}};
+            T Pp[6], FP[3][3];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) Pp[k] = in.P[k];
+            L.template predict<1>(dt, xp, Pp, FP);
+            // P_p = L D L^T (unit lower L).  The pivots' reciprocals are IEEE divisions, not the
+            // updates' rcp_nr<kRefNewton>: P_f - C P_p C^T cancels (between applied updates P_s is
+            // orders of magnitude below P_f) and a relative error e of a pivot's reciprocal is the
+            // same wrong P_p^-1 in all three rows of C, so it reaches P_s as e P_f.  Measured against
+            // the longdouble truth at T = 300, in units of the plain float64 NumPy smoother's own
+            // error, budget 8 (profiles/rts_smoother/reciprocal_forms.log): with rcp_nr<kRefNewton>
+            // (2^-46) log det P_s reached 8.4 at the first case that failed; with a step of
+            // iterative refinement of C on top, P_s 8.9 and log det 36 (the residual rounds at
+            // eps |C| |P_p|); with divisions at most 2.0 and 4.8.  Three divisions a step
+            const T d0 = Pp[0];
+            const T i0 = T(1) / d0;
+            const T l10 = Pp[1] * i0, l20 = Pp[2] * i0;
+            const T v0 = l10 * d0;
+            const T d1 = fmaT(-l10, v0, Pp[3]);
+            const T i1 = T(1) / d1;
+            const T l21 = fmaT(-l20, v0, Pp[4]) * i1;
+            const T d2 = fmaT(-l21, l21 * d1, fmaT(-l20, l20 * d0, Pp[5]));
+            const T i2 = T(1) / d2;
+            bad = bad || !(d0 > T(0) && d1 > T(0) && d2 > T(0));
+            // C = (P_f F^T) P_p^-1, row i: P_p c = row i of (F P_f)^T = column i of F P_f
+            T C[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const T w0 = FP[0][i];
+                const T w1 = fmaT(-l10, w0, FP[1][i]);
+                const T w2 = fmaT(-l21, w1, fmaT(-l20, w0, FP[2][i]));
+                const T c2 = w2 * i2;
+                const T c1 = fmaT(-l21, c2, w1 * i1);
+                const T c0 = fmaT(-l20, c2, fmaT(-l10, c1, w0 * i0));
+                C[i][0] = c0, C[i][1] = c1, C[i][2] = c2;
+            }
+            T dx[3], D[6];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dx[k] = xs[0][k] - xp[0][k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) D[k] = Ps[k] - Pp[k];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                xs[0][i] = fmaT(C[i][2], dx[2], fmaT(C[i][1], dx[1], fmaT(C[i][0], dx[0], in.x[i])));
+            T CD[3][3];  // C D
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    CD[i][j] = fmaT(C[i][2], D[tri<3>(2, j)], fmaT(C[i][1], D[tri<3>(1, j)], C[i][0] * D[tri<3>(0, j)]));
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = i; j < 3; ++j)
+                    Ps[tri<3>(i, j)] =
+                        fmaT(CD[i][2], C[j][2], fmaT(CD[i][1], C[j][1], fmaT(CD[i][0], C[j][0], in.P[tri<3>(i, j)])));
+            if (!L.pva) {  // the inert state, as after the forward run's updates
+                xs[0][2] = T(0);
+                Ps[2] = Ps[4] = T(0);
+                Ps[5] = T(1);
+            }
+        }
+        if (group_any(live && bad) || st != 0) poison();
+        store_row(t);
+    };
+    ring_run<kSmoothDepth, T, SmoothIn<T>>(n, load, step);
+    if (a.sm_status) {
+        const auto rs = span_rsrc(a.sm_status, 0, uint32_t(a.B) * 4u, 1);
+        __builtin_amdgcn_raw_buffer_store_b32(uint32_t(st), rs, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
     }
 }
 
@@ -5012,6 +5249,19 @@ hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t
         KF_MODEL_DISPATCH(model, f64, ref_sweep_kernel<T, M, false, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
     else
         KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
+    return hipGetLastError();
+}
+
+hipError_t launch_ref_smooth(int model, const SmoothArgs& a, hipStream_t stream) {
+    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || !a.filt_x || !a.filt_P || !a.etype || !a.dt)
+        return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
+    if (a.consts)
+        KF_MODEL_DISPATCH(model, true, if constexpr (sizeof(T) == 8)
+                                           ref_smooth_kernel<T, M, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
+    else
+        KF_REF_DISPATCH(model, true, a.kc, if constexpr (sizeof(T) == 8)
+                                               ref_smooth_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
     return hipGetLastError();
 }
 

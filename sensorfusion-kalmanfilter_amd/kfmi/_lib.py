@@ -127,6 +127,7 @@ SIGNATURES = {
     'kf_run_sweep': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_run_sweep_params': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_run_sweep_scores': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'kf_smooth_sweep': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kf_consts_rows': (_i, [_i, ctypes.POINTER(_i)]),
     'kf_run_tails': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
     'kf_stream_check': (_i, [_vp, _vp, _vp]),

@@ -91,6 +91,7 @@ SCORE_ROWS = {'gps_n': _lib.KF_SCORE_GPS_N, 'gps_nis': _lib.KF_SCORE_GPS_NIS,
 assert len(SCORE_ROWS) == _lib.KF_SCORE_ROWS
 
 SweepScores = collections.namedtuple('SweepScores', 'scores n_updated traj logdet updated ckpt_x ckpt_P')
+SmoothedSweep = collections.namedtuple('SmoothedSweep', 'x P traj logdet status')
 
 
 def innovation_nll(scores, model, sensor):
@@ -553,6 +554,55 @@ class BatchedKF:
             check(_lib.lib().kf_run_sweep_params(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(thr), _ptr(tab),
                                                  _ptr(tr), _ptr(ld), _ptr(up), _ptr(nu), *ck))
         return tr, ld, up, nu, cx, cP, sc
+
+    def _consts_tab(self, consts):
+        """run_sweep's ``consts`` (a [R, B] float64 table or a list of B ModelConsts) on the device."""
+        R = consts_rows(self.model)
+        if isinstance(consts, (list, tuple)):
+            if len(consts) != self.batch:
+                raise KFError(_lib.KF_EINVAL, f'consts: {len(consts)} constant sets for B = {self.batch} filters')
+            consts = consts_table(self.model, consts)
+        if isinstance(consts, np.ndarray):
+            consts = torch.from_numpy(np.ascontiguousarray(consts))
+        if not torch.is_tensor(consts) or consts.dtype != torch.float64 or tuple(consts.shape) != (R, self.batch):
+            raise KFError(_lib.KF_EINVAL, f'consts: expected a float64 [R, B] = {(R, self.batch)} table or a list of '
+                                          f'ModelConsts, got {getattr(consts, "dtype", type(consts))} '
+                                          f'{tuple(getattr(consts, "shape", ()))}')
+        return self._dev(consts, (R, self.batch), 'consts', torch.float64)
+
+    def smooth_sweep(self, etype, dt, filt_x, filt_P, consts=None, x=True, P=False, traj=False, logdet=False,
+                     inplace=False):
+        """The RTS smoother over a sweep's filtered record (kf_smooth_sweep): etype [T] uint8 and dt
+        [T] float64 as run_sweep took them, filt_x [T, n, B] and filt_P [T, rows, B] the ckpt_x /
+        ckpt_P of run_sweep(checkpoint_every=1) (device tensors or arrays), ``consts`` as in
+        run_sweep (None: the handle's constants; only the Q rates are read).  An f64 ref15 / ref8
+        handle, whose state and status are not touched.  Returns SmoothedSweep(x [T, n, B], P [T,
+        rows, B], traj [T, W, B], logdet [T, B], status [B] int32), None where not asked for; row
+        T - 1 is the filtered row, and row t is row t + 1 wherever etype[t + 1] is NONE.
+        ``inplace``: x and P (where asked for) overwrite filt_x / filt_P, which must then be device
+        tensors.  A filter whose record is not positive definite (or holds a NaN) has NaN rows from
+        there down to 0 and KF_ENOTSPD in ``status``."""
+        if self.model not in REF_MODELS:
+            raise ValueError('smooth_sweep needs a ref15 or ref8 handle')
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'smooth_sweep: needs an f64 handle')
+        T = int(etype.shape[0])
+        if inplace and not (torch.is_tensor(filt_x) and torch.is_tensor(filt_P) and filt_x.device == self.device
+                            and filt_P.device == self.device and filt_x.is_contiguous() and filt_P.is_contiguous()):
+            raise KFError(_lib.KF_EINVAL, 'smooth_sweep: inplace needs contiguous device tensors filt_x / filt_P')
+        fx = self._dev(filt_x, (T, self.n, self.batch), 'filt_x')
+        fP = self._dev(filt_P, (T, self.ntri, self.batch), 'filt_P')
+        tab = self._consts_tab(consts) if consts is not None else None
+        et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
+        dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
+        sx = (fx if inplace else self.empty(T, self.n, self.batch)) if x else None
+        sP = (fP if inplace else self.empty(T, self.ntri, self.batch)) if P else None
+        tr = self.empty(T, TRAJ_WIDTH[self.model], self.batch) if traj else None
+        ld = self.empty(T, self.batch) if logdet else None
+        st = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        check(_lib.lib().kf_smooth_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(tab), _ptr(fx), _ptr(fP), _ptr(sx),
+                                         _ptr(sP), _ptr(tr), _ptr(ld), _ptr(st), self._stream()))
+        return SmoothedSweep(sx, sP, tr, ld, st)
 
     def run_tails(self, etype, dt, payload, lo, hi, thresholds, src_x=None, src_P=None, src_row=None, src_col=None,
                   counts=False):

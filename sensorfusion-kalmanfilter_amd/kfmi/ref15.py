@@ -594,15 +594,36 @@ class AdaptiveSweep:
     previous_time) of the driver over [start_idx, end_idx), from the checkpoint at or before
     end_idx (every ``checkpoint_every`` array entries) and a one-filter sweep over the fewer than
     checkpoint_every events after it.  ``warm_starts(index, end_idxs)``: the list of
-    warm_start(index[w], end_idxs[w]), every tail in one launch (kf_run_tails)."""
+    warm_start(index[w], end_idxs[w]), every tail in one launch (kf_run_tails).
+
+    ``smooth=True`` (f64 only; 'full' keeps the smoothed covariances too) adds the fixed-interval
+    smoother: the forward launch runs with checkpoint_every = 1, so its checkpoint arrays are the
+    filtered record (336 B per entry and filter; KFError(KF_ENOMEM) before anything runs if the
+    records do not fit the device's free memory) and warm_start reads its row directly, then one
+    kf_smooth_sweep runs over it.  ``smoothed(i)``: (states, logdets) shaped like result(i)'s,
+    the estimate of every entry given the whole window.  result(i) and warm_start are the
+    smooth=False object's.  The smoothed positions with the entries' times are a ``track`` as
+    they are:
+        states, _ = AdaptiveSweep(events, [-np.inf], smooth=True).smoothed(0)
+        track = (np.array([s[0] for s in states]), np.array([s[1:4] for s in states]))
+        ParameterSweep(events, sets, scores=True, track=track).best('pos_rmse')"""
 
     def __init__(self, events, thresholds, start_idx=None, end_idx=None, initial_pt=None, initial_state=None,
-                 dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096, scores=False, track=None):
+                 dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096, scores=False, track=None,
+                 smooth=False):
         from .ingest import events_dt
         self.thresholds = np.array(thresholds, dtype=np.float64).reshape(-1)
         self.dtype, self.consts, self.records = dtype, consts, bool(records)
         self.scored, self.scores = bool(scores), None
         self.every = int(checkpoint_every)
+        self.smooth = smooth
+        if smooth:
+            if smooth is not True and smooth != 'full':
+                raise ValueError(f'smooth: True, False or \'full\', got {smooth!r}')
+            if dtype != 'f64':
+                raise _lib.KFError(_lib.KF_EINVAL, f'smooth=True needs dtype=\'f64\', got {dtype!r} (the smoother '
+                                                   f'is f64 only)')
+            self.every = 1  # the filtered record is the checkpoint array: a row per entry
         self.n_updates = np.zeros(len(self.thresholds), np.int64)
         self.empty = True  # a cold window without a fix: the driver returns None
         self._kf1, self._kft = None, {}  # warm_start's one-filter handle; warm_starts' handles by batch size
@@ -703,6 +724,14 @@ class AdaptiveSweep:
             rows = track_positions(tt, tp, self._t)
             rows[~self._keep] = np.nan
             self._track = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+        if smooth:
+            # the filtered record (15 + 27 rows) and the smoothed records kept, 8 B each per entry and filter
+            rows = 15 + 27 + 6 + 1 + (27 if smooth == 'full' else 0)
+            need = (T + 1) * rows * B * 8
+            free = torch.cuda.mem_get_info(dev)[0]
+            if need > free:
+                raise _lib.KFError(_lib.KF_ENOMEM, f'smooth: the filtered and smoothed records of {T + 1} entries x '
+                                                   f'{B} filters need {need} B, the device has {free} B free')
         kf = BatchedKF('ref15', B, dtype, device=dev.index or 0, params=_params(consts))
         try:
             kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
@@ -720,8 +749,28 @@ class AdaptiveSweep:
             self._x, self._Pb = kf.state()
             self._status = kf.status()
             self.n_updates = nu.cpu().numpy().astype(np.int64)
+            if smooth:
+                sm = kf.smooth_sweep(self._et, self._dt, self._cx, self._cP, consts=self._table, x=False,
+                                     P=smooth == 'full', traj=True, logdet=True)
+                self._sm_traj, self._sm_ld, self._sm_P, self._sm_status = sm.traj, sm.logdet, sm.P, sm.status
         finally:
             kf.close()
+
+    def smoothed(self, i):
+        """(states, logdets) of the fixed-interval smoother over thresholds[i]'s run (needs
+        smooth=True): shaped like the first two items of result(i) and over the same kept entries,
+        every state the estimate given the WHOLE window (kf_smooth_sweep over the filtered record),
+        logdets the log det of the smoothed covariances.  The leading entry is the smoothed initial
+        state; the last equals result(i)'s.  None where result(i) is None.  smooth='full' also keeps
+        the smoothed covariances, block-packed [entries, 27, B] on the device, as ``_sm_P``."""
+        if not self.smooth:
+            raise ValueError('AdaptiveSweep.smoothed needs smooth=True')
+        if self.empty:
+            return None
+        keep = torch.from_numpy(self._keep).to(self.dev)
+        traj = self._sm_traj[:, :, i][keep].cpu().numpy()
+        ld = self._sm_ld[:, i][keep].cpu().numpy()
+        return _stream_states(self._t[self._keep], traj), ld.tolist()
 
     def close(self):
         if getattr(self, '_kf1', None) is not None:
@@ -850,6 +899,22 @@ def _scores_dict(table):
     return d
 
 
+def run_smoothed_kalman_filter(events, start_idx=None, end_idx=None, R_threshold=None, consts=None, initial_pt=None,
+                               initial_state=None, device=0):
+    """run_adaptive_threshold_kalman_filter (R_threshold None: the ungated filter) followed by the
+    fixed-interval smoother over its run, f64: an AdaptiveSweep(smooth=True) of the one threshold.
+    Returns result(0) + smoothed(0): (states, logdets, P, previous_time, measurement_times,
+    smoothed_states, smoothed_logdets), or None where the driver returns None.  The reference has
+    no smoother; the smoothed states are the estimate of every entry given the whole window."""
+    thr = -float('inf') if R_threshold is None else float(R_threshold)
+    sw = AdaptiveSweep(events, [thr], start_idx, end_idx, initial_pt, initial_state, 'f64', device, consts, smooth=True)
+    try:
+        r = sw.result(0)
+        return None if r is None else r + sw.smoothed(0)
+    finally:
+        sw.close()
+
+
 def run_adaptive_threshold_sweep(events, thresholds, **kw):
     """The AdaptiveSweep of ``events`` under ``thresholds`` (its keyword arguments)."""
     return AdaptiveSweep(events, thresholds, **kw)
@@ -881,7 +946,7 @@ class ParameterSweep(AdaptiveSweep):
 
     def __init__(self, events, consts_list, thresholds=None, start_idx=None, end_idx=None, initial_pt=None,
                  initial_state=None, dtype='f64', device=0, records=True, checkpoint_every=4096, track=None,
-                 scores=False):
+                 scores=False, smooth=False):
         self._sets = list(consts_list)
         if thresholds is None:
             thresholds = np.full(len(self._sets), -np.inf)
@@ -892,7 +957,7 @@ class ParameterSweep(AdaptiveSweep):
             if not isinstance(c, ModelConsts) or c.model != 'ref15':
                 raise ValueError('ParameterSweep: consts_list holds ModelConsts(\'ref15\', ...)')
         super().__init__(events, thresholds, start_idx, end_idx, initial_pt, initial_state, dtype, device, None,
-                         records, checkpoint_every, scores, track)
+                         records, checkpoint_every, scores, track, smooth=smooth)
         self.consts_list = self._sets
 
     def warm_starts(self, index, end_idxs):
