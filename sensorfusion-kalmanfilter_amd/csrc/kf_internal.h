@@ -69,7 +69,7 @@ struct RefArgs {
     const void* payload;     // [T][9][B]: GPS (easting, northing, altitude, -), IMU (roll, pitch,
                              // yaw, wx, wy, wz, ax, ay, az) as in kf_workers.py:367
     void* x;                 // [N][B]
-    void* P;                 // [NBLK][B] block-packed covariance (see kf_ref.hip)
+    void* P;                 // [NBLK][B] block-packed covariance (see kf_ref_model.h)
     int32_t* status;         // [B]
     const void* x0;          // reset: [N][B] or nullptr
     void* traj;              // [T][NTRAJ][B] x[0:NTRAJ] after each event, or nullptr
@@ -506,7 +506,7 @@ struct Ref15SchedArgs {
 
 enum class Op { Run, Predict, Update, Step, Reset };  // Step: predict + update (kf_capi's deferral)
 
-// Launchers (kf_cv.hip, kf_ref.hip).  Return hipSuccess or the launch error.
+// Launchers (kf_cv.hip, kf_ref.hip, kf_ref_chain.hip).  Return hipSuccess or the launch error.
 hipError_t launch_cv(int axes, bool f64, Op op, const CvArgs& a, hipStream_t stream);
 // *flag |= 1 if any filter's P couples different axes (flag: device int, zeroed by the caller).
 hipError_t launch_cv_offblock(int axes, bool f64, const CvArgs& a, int* flag, hipStream_t stream);
@@ -518,6 +518,10 @@ hipError_t launch_copy(void* dst, const void* src, size_t bytes, hipStream_t str
 // per axis chain (few filters), one lane per filter with inputs staged through LDS by DMA
 constexpr int kEventsLane = 0, kEventsChain = 1, kEventsLds = 2, kEventsGated = 3;  // gated: B = 1 look-ahead
 hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t stream, int variant);
+// launch_ref_events' kEventsChain and kEventsGated variants, whose kernels are kf_ref_chain.hip's
+// (internal: launch_ref_events has checked the arguments and forwards here)
+__attribute__((visibility("hidden"))) hipError_t launch_ref_events_chain(int model, bool f64, const RefArgs& a,
+                                                                         hipStream_t stream, int variant);
 // the chain kernel in stream mode (a.s_len > 0); nv = 4: the map pass, four state variants per
 // filter sharing its covariance (state bank of 4 B columns)
 hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv = 1);

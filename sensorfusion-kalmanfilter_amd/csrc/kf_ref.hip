@@ -1,407 +1,15 @@
-// gfx950 kernels for the reference's chain-structured GPS+IMU models on per-filter event
-// streams — KF_MODEL_REF15 (kf_workers.py:493-614) and KF_MODEL_REF8 (hw5_2.py:219-311) — and
-// the brute-force combination search and sensor scheduling built on the 15-state one
-// (kf_workers.py:22-213, 826-957, 1218-1392).
-//
-// Structure exploited (exact, not an approximation): F(dt) (kf_workers.py:500-516,
-// hw5_2.py:221-230) couples a state only within its axis chain (pos_i, vel_i, acc_i) or
-// (att_i, rate_i); Q, R_gps, R_imu and the reference's P0 are diagonal; H_gps selects pos_i and
-// H_imu = I.  So every covariance reachable from a diagonal P0 is block-diagonal — 3x3
-// (pos, vel, acc) blocks and 2x2 (att, rate) blocks — and the reference's own dense arithmetic
-// keeps the off-block entries at exactly 0.0 (checked on its outputs, tests/golden/ref15_*.npz).
-// A lane therefore runs small chain filters: REF15 = 3 pva + 3 aw chains (27 covariance entries
-// instead of 120), REF8 = 2 pva (x, y) + 1 aw (theta) chain (15 instead of 36); same numbers.
-//
-// Block-packed covariance rows ([NBLK][B] in HBM):
-//   rows 6c .. 6c+5 : pva chain c upper triangle (pp pv pa vv va aa), c = 0..NP-1
-//   rows 6NP+3c .. 6NP+3c+2 : aw chain c upper triangle (tt tw ww), c = 0..NA-1
-// State x [N][B] in the reference's order.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <type_traits>
-
-#include "kf_common.h"
-#include "kf_internal.h"
+// gfx950 kernels for the reference's chain-structured GPS+IMU models (the model layer and the
+// layout: kf_ref_model.h): the one-lane-per-filter kernels on per-filter event streams, the phases
+// of the time-parallel stream run, the brute-force search, the scheduler and the schedule search.
+// The 8-lanes-per-filter kernels are kf_ref_chain.hip's; this unit reads ChainLane's tables.
+#include "kf_ref_chainlane.h"
 
 namespace kfmi {
 namespace {
 
-// Read-only device tables (the handle's custom constants, a search's events and binomials) read
-// through the constant address space: a wave-uniform entry then becomes a scalar load.  Through a
-// generic pointer the compiler cannot prove that a kernel's own stores leave them alone, so it
-// loads them with vector loads, whose vmcnt wait also waits for every store issued before them
-// (on gfx950 vmcnt counts loads and stores, in order).  Every such table is written by the host
-// before the launch and never by a kernel.
-template <typename T>
-__device__ __forceinline__ __attribute__((address_space(4))) const T* ro(const T* p) {
-    return (__attribute__((address_space(4))) const T*)p;
-}
-typedef __attribute__((address_space(4))) const double ro_double;
-typedef __attribute__((address_space(4))) const uint64_t ro_u64;
-
-using namespace dev;
-
-constexpr int kGps = 0, kImu = 1;  // KF_EVENT_GPS / KF_EVENT_IMU; 2 = predict only, 255 = none
-// Newton steps on the update's pivot reciprocals (see sel_update)
-constexpr int kRefNewton = 1;
-// Covariance update of the reference models.  fp64 takes the reference's own form
-// P = (I - K H) P (kf_workers.py:711, hw5_2.py:358, 376) over the packed upper triangle, its
-// observed rows as K R (sel_update_nv: the same value without 1 - K's cancellation); fp32 keeps
-// Joseph's, which the fp32 parity gate needs (the simple form drifts there).
-// KF_REF_JOSEPH_F64=1 builds fp64 with Joseph too (the A/B arm).
-#ifndef KF_REF_JOSEPH_F64
-#define KF_REF_JOSEPH_F64 0
-#endif
-template <typename T>
-constexpr bool kRefJoseph = sizeof(T) == 4 || KF_REF_JOSEPH_F64 != 0;
-// The IMU pseudo-measurement's H = I chain updates take P = K R (sel_update_nv's GAIN_R: the
-// same value as (I - K)P, without its cancellation), in both precisions; KF_REF_GAIN_R=0 builds
-// the A/B arm without it (fp64: the cancelling P - K P on every row; fp32: Joseph's).
-#ifndef KF_REF_GAIN_R
-#define KF_REF_GAIN_R 1
-#endif
-constexpr bool kRefGainR = KF_REF_GAIN_R != 0;
-
-
-// Noise constants shared by both reference models (kf_workers.py:519-544, 581-614;
-// hw5_2.py:233-251, 280-304).
-constexpr double kQPos = 5.0, kQAtt = 0.05, kQVel = 1.0, kQRate = 0.1, kQAcc = 2.0;
-constexpr double kRGps = 3.0;
-constexpr double kRPos = 50.0, kRAtt = 0.05, kRVel = 10.0, kRRate = 0.1, kRAcc = 100.0;
-
-// KF_MODEL_REF15: x = (pos xyz, att rpy, vel xyz, rate xyz, acc xyz) (kf_workers.py:493-517).
-struct M15 {
-    static constexpr int N = 15, NP = 3, NA = 3, NTRAJ = 6, NBLK = 27;
-    __device__ static constexpr int pva(int c, int k) { return c + 6 * k; }          // (i, 6+i, 12+i)
-    __device__ static constexpr int aw(int c, int k) { return 3 + c + 6 * k; }       // (3+i, 9+i)
-    __device__ static constexpr int imu_acc(int c) { return 6 + c; }                 // ax, ay, az
-    __device__ static constexpr int imu_att(int c) { return c; }                     // roll, pitch, yaw
-    __device__ static constexpr int imu_rate(int c) { return 3 + c; }                // wx, wy, wz
-    static constexpr double P0Pos = 10000.0, P0Att = 1000.0, P0Vel = 1000.0, P0Rate = 1000.0,
-                            P0Acc = 10000.0;  // kf_workers.py:651
-};
-
-// KF_MODEL_REF8: x = (x, y, theta, vx, vy, theta_dot, ax, ay) (hw5_2.py:219-231); the IMU
-// pseudo-measurement takes yaw as theta and wz as theta_dot (hw5_2.py:355-362).
-struct M8 {
-    static constexpr int N = 8, NP = 2, NA = 1, NTRAJ = 3, NBLK = 15;
-    __device__ static constexpr int pva(int c, int k) { return c + 3 * k; }          // (i, 3+i, 6+i)
-    __device__ static constexpr int aw(int, int k) { return 2 + 3 * k; }             // (2, 5)
-    __device__ static constexpr int imu_acc(int c) { return 6 + c; }                 // ax, ay
-    __device__ static constexpr int imu_att(int) { return 2; }                       // yaw
-    __device__ static constexpr int imu_rate(int) { return 5; }                      // wz
-    static constexpr double P0Pos = 1000.0, P0Att = 100.0, P0Vel = 100.0, P0Rate = 100.0,
-                            P0Acc = 1000.0;  // hw5_2.py:317-326
-};
-
-// Noise constants of a chain.  CUSTOM = false: the reference's, compile-time literals (the
-// default, and the code every bench row runs); CUSTOM = true: a caller's diagonal Q rates, R_imu,
-// R_gps and P0 per state (kf_params -> RefConsts, the handle's device copy at kc), read by
-// wave-uniform scalar loads.  Both give Chains the same operations in the same order.
-template <bool CUSTOM, class M, typename T>
-__device__ __forceinline__ void pva_noise(const RefConsts* kc, int c, T (&q)[3], T (&r)[6], T& rg) {
-    if constexpr (CUSTOM) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = T(ro(kc)->q[M::pva(c, k)]);
-        r[0] = T(ro(kc)->r_imu[M::pva(c, 0)]);
-        r[3] = T(ro(kc)->r_imu[M::pva(c, 1)]);
-        r[5] = T(ro(kc)->r_imu[M::pva(c, 2)]);
-        rg = T(ro(kc)->r_gps[c]);
-    } else {
-        q[0] = T(kQPos);
-        q[1] = T(kQVel);
-        q[2] = T(kQAcc);
-        r[0] = T(kRPos);
-        r[3] = T(kRVel);
-        r[5] = T(kRAcc);
-        rg = T(kRGps);
-    }
-    r[1] = r[2] = r[4] = T(0);
-}
-template <bool CUSTOM, class M, typename T>
-__device__ __forceinline__ void aw_noise(const RefConsts* kc, int c, T (&q)[2], T (&r)[3]) {
-    if constexpr (CUSTOM) {
-        q[0] = T(ro(kc)->q[M::aw(c, 0)]);
-        q[1] = T(ro(kc)->q[M::aw(c, 1)]);
-        r[0] = T(ro(kc)->r_imu[M::aw(c, 0)]);
-        r[2] = T(ro(kc)->r_imu[M::aw(c, 1)]);
-    } else {
-        q[0] = T(kQAtt);
-        q[1] = T(kQRate);
-        r[0] = T(kRAtt);
-        r[2] = T(kRRate);
-    }
-    r[1] = T(0);
-}
-
-template <typename T, class M, bool CUSTOM = false>
-struct Chains {
-    T x[M::N];
-    T pva[M::NP][6];  // per chain: (pos, vel, acc) packed upper 3x3
-    T aw[M::NA][3];   // per chain: (att, rate) packed upper 2x2
-    const RefConsts* kc = nullptr;  // CUSTOM: the noise constants (kf_params)
-    // Chain predict x = F x, P = F P F^T + Q for a block whose F row i is
-    // e_i + dt e_{i+1} + dt^2/2 e_{i+2} (kf_workers.py:500-516).
-    template <int NB>
-    __device__ static __forceinline__ void chain_predict(T (&xb)[NB], T (&Pb)[NB * (NB + 1) / 2], T dt,
-                                                         const T (&q)[NB]) {
-        const T c[3] = {T(1), dt, T(0.5) * dt * dt};
-        // the d / e loops run a constant 2 trips with a compile-time guard: a trip count of
-        // min(NB - i, 3) - 1 was left as a runtime loop with indexed register reads (s_set_gpr_idx)
-        T xn[NB];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            T s = xb[i];
-#pragma unroll
-            for (int d = 1; d < 3; ++d)
-                if (i + d < NB) s = fmaT(c[d], xb[i + d], s);
-            xn[i] = s;
-        }
-        T FP[NB][NB];
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                T s = Pb[tri<NB>(i, j)];
-#pragma unroll
-                for (int d = 1; d < 3; ++d)
-                    if (i + d < NB) s = fmaT(c[d], Pb[tri<NB>(i + d, j)], s);
-                FP[i][j] = s;
-            }
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int j = i; j < NB; ++j) {
-                T s = FP[i][j];
-#pragma unroll
-                for (int e = 1; e < 3; ++e)
-                    if (j + e < NB) s = fmaT(FP[i][j + e], c[e], s);
-                Pb[tri<NB>(i, j)] = (i == j) ? s + q[i] * dt : s;
-            }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) xb[i] = xn[i];
-    }
-
-    __device__ __forceinline__ void predict(T dt) {
-#pragma unroll
-        for (int c = 0; c < M::NP; ++c) {
-            T qpva[3], r[6], rg;
-            pva_noise<CUSTOM, M>(kc, c, qpva, r, rg);
-            T xb[3];
-            get_pva(c, xb);
-            chain_predict<3>(xb, pva[c], dt, qpva);
-            put_pva(c, xb);
-        }
-#pragma unroll
-        for (int c = 0; c < M::NA; ++c) {
-            T qaw[2], r[3];
-            aw_noise<CUSTOM, M>(kc, c, qaw, r);
-            T xa[2];
-            get_aw(c, xa);
-            chain_predict<2>(xa, aw[c], dt, qaw);
-            put_aw(c, xa);
-        }
-    }
-
-    __device__ __forceinline__ void get_pva(int c, T (&xb)[3]) const {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xb[k] = x[M::pva(c, k)];
-    }
-    __device__ __forceinline__ void put_pva(int c, const T (&xb)[3]) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[M::pva(c, k)] = xb[k];
-    }
-    __device__ __forceinline__ void get_aw(int c, T (&xa)[2]) const {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) xa[k] = x[M::aw(c, k)];
-    }
-    __device__ __forceinline__ void put_aw(int c, const T (&xa)[2]) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) x[M::aw(c, k)] = xa[k];
-    }
-
-    // GPS fix (kf_workers.py:694-697, hw5_2.py:341-349): H selects pos_c in each (pos, vel,
-    // acc) chain, R = 3; z = (easting, northing[, altitude]).
-    template <bool POISON = true>
-    __device__ __forceinline__ bool update_gps(const T (&z)[3]) {
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < M::NP; ++c) {
-            T q[3], r[6], rg;
-            pva_noise<CUSTOM, M>(kc, c, q, r, rg);
-            const T R[1] = {rg};
-            T xb[3];
-            get_pva(c, xb);
-            const T zb[1] = {z[c]};
-            ok = sel_update<3, 1, true, T, kRefNewton, POISON, kRefJoseph<T>, kRefGainR>(xb, pva[c], zb, R) && ok;
-            put_pva(c, xb);
-        }
-        return ok;
-    }
-
-    // IMU pseudo-measurement (kf_workers.py:698-706, hw5_2.py:352-366): Z from the PREDICTED
-    // state and the raw sample, H = I, R = diag(50, 0.05, 10, 0.1, 100 per group).  imu = (roll,
-    // pitch, yaw, wx, wy, wz, ax, ay, az).
-    // `imu` is any indexable payload: a register array, or an LDS image (ref_events_lds_kernel)
-    template <bool POISON = true, class Pay>
-    __device__ __forceinline__ bool update_imu(const Pay& imu, T dt) {
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < M::NP; ++c) {
-            T q[3], Rp[6], rg;
-            pva_noise<CUSTOM, M>(kc, c, q, Rp, rg);
-            T xb[3];
-            get_pva(c, xb);
-            const T a = imu[M::imu_acc(c)];
-            const T V = fmaT(a, dt, xb[1]);   // V = x_v + a dt
-            const T X = fmaT(V, dt, xb[0]);   // X = x_p + V dt
-            const T zb[3] = {X, V, a};
-            ok = sel_update<3, 3, true, T, kRefNewton, POISON, kRefJoseph<T>, kRefGainR>(xb, pva[c], zb, Rp) && ok;
-            put_pva(c, xb);
-        }
-#pragma unroll
-        for (int c = 0; c < M::NA; ++c) {
-            T q[2], Ra[3];
-            aw_noise<CUSTOM, M>(kc, c, q, Ra);
-            T xa[2];
-            get_aw(c, xa);
-            const T za[2] = {imu[M::imu_att(c)], imu[M::imu_rate(c)]};
-            ok = sel_update<2, 2, true, T, kRefNewton, POISON, kRefJoseph<T>, kRefGainR>(xa, aw[c], za, Ra) && ok;
-            put_aw(c, xa);
-        }
-        return ok;
-    }
-
-    // slogdet of the full P = sum over the chain blocks (kf_workers.py:716-717): the product of
-    // the blocks' determinants, division-free per block (det3_scaled / det2) and one reciprocal
-    // for the pva pivots; fp32 renormalises after every block (three pva blocks reach 1e48).
-    __device__ __forceinline__ T logdet() const {
-        int ex;
-        const T prod = det_mant(ex);
-        const T ld = log_mant(prod, ex);
-        return prod == prod ? ld : quiet_nan<T>();
-    }
-    // the same determinant before its log: mantissa in [0.5, 1) (NaN unless positive definite)
-    // times 2^ex
-    __device__ __forceinline__ T det_mant(int& ex) const {
-        constexpr bool kNarrow = sizeof(T) == 4;
-        T num = T(1), den = T(1);
-        ex = 0;
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < M::NP; ++c) {
-            det3_scaled<T>(pva[c], num, den, ok);
-            if (kNarrow || c == M::NP - 1) renorm(num, ex);
-        }
-#pragma unroll
-        for (int c = 0; c < M::NA; ++c) {
-            det2<T>(aw[c], num, ok);
-            if (kNarrow) renorm(num, ex);
-        }
-        T prod = num * rcp_nr<kRefNewton>(den);
-        renorm(prod, ex);
-        return ok ? prod : quiet_nan<T>();
-    }
-
-    __device__ __forceinline__ void reset_cov() {
-        const T p[6] = {T(M::P0Pos), T(0), T(0), T(M::P0Vel), T(0), T(M::P0Acc)};
-        const T w[3] = {T(M::P0Att), T(0), T(M::P0Rate)};
-#pragma unroll
-        for (int c = 0; c < M::NP; ++c)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) pva[c][k] = p[k];
-#pragma unroll
-        for (int c = 0; c < M::NA; ++c)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) aw[c][k] = w[k];
-        if constexpr (CUSTOM) {  // P0 = diag(p0) in the model's state order
-#pragma unroll
-            for (int c = 0; c < M::NP; ++c) {
-                pva[c][0] = T(ro(kc)->p0[M::pva(c, 0)]);
-                pva[c][3] = T(ro(kc)->p0[M::pva(c, 1)]);
-                pva[c][5] = T(ro(kc)->p0[M::pva(c, 2)]);
-            }
-#pragma unroll
-            for (int c = 0; c < M::NA; ++c) {
-                aw[c][0] = T(ro(kc)->p0[M::aw(c, 0)]);
-                aw[c][2] = T(ro(kc)->p0[M::aw(c, 1)]);
-            }
-        }
-    }
-
-    // block-packed covariance row r (see the file comment)
-    __device__ __forceinline__ T& blk(int r) { return r < 6 * M::NP ? pva[r / 6][r % 6] : aw[(r - 6 * M::NP) / 3][(r - 6 * M::NP) % 3]; }
-    __device__ __forceinline__ T blk(int r) const { return r < 6 * M::NP ? pva[r / 6][r % 6] : aw[(r - 6 * M::NP) / 3][(r - 6 * M::NP) % 3]; }
-
-    __device__ __forceinline__ void load(const void* xbase, const void* Pbase, uint32_t rb, uint32_t off) {
-#pragma unroll
-        for (int i = 0; i < M::N; ++i) x[i] = ldb<T>(xbase, i, rb, off);
-#pragma unroll
-        for (int r = 0; r < M::NBLK; ++r) blk(r) = ldb<T>(Pbase, r, rb, off);
-    }
-
-    __device__ __forceinline__ void store(void* xbase, void* Pbase, uint32_t rb, uint32_t off) const {
-#pragma unroll
-        for (int i = 0; i < M::N; ++i) stb(xbase, i, rb, off, x[i]);
-        store_cov(Pbase, 0, rb, off);
-    }
-
-    // covariance rows at row offset r0 of a [.][B] array (r0 = t * NBLK for a per-step record)
-    __device__ __forceinline__ void store_cov(void* Pbase, int64_t r0, uint32_t rb, uint32_t off) const {
-#pragma unroll
-        for (int r = 0; r < M::NBLK; ++r) stb(Pbase, r0 + r, rb, off, blk(r));
-    }
-
-    __device__ __forceinline__ void fill_nan() {
-#pragma unroll
-        for (int i = 0; i < M::N; ++i) x[i] = quiet_nan<T>();
-#pragma unroll
-        for (int r = 0; r < M::NBLK; ++r) blk(r) = quiet_nan<T>();
-    }
-
-    // One event of the reference loop (kf_workers.py:682-717): predict over dt, then the GPS or
-    // IMU update; with `gate`, the update only when logdet(P_pred) > threshold
-    // (run_adaptive_threshold_kalman_filter, kf_workers.py:1023-1025).  Returns whether the
-    // update was applied; `ok` turns false on a non-positive-definite S.
-    // POISON = false for callers that fill the filter with NaN when `ok` turns false
-    template <bool POISON = true, class Pay>
-    __device__ __forceinline__ bool event(int type, T dt, const Pay& pay, bool gate, T threshold, bool& ok) {
-        predict(dt);
-        bool apply = (type == kGps || type == kImu);
-        if (gate && apply) apply = logdet() > threshold;
-        if (apply) {
-            if (type == kGps) {
-                const T z[3] = {pay[0], pay[1], pay[2]};  // (easting, northing, altitude)
-                ok = update_gps<POISON>(z) && ok;
-            } else {
-                ok = update_imu<POISON>(pay, dt) && ok;
-            }
-        }
-        return apply;
-    }
-};
-
 // ------------------------------------------------------------------------------------
 // Per-filter event streams (kf_run_events).
 // ------------------------------------------------------------------------------------
-// GATES (kf_run_events_gates): filter f's update is gated by its own a.thresholds[f], in the
-// sweep's conventions (gate_of); the instantiations without it are kf_run_events' as before.
-template <typename T>
-struct FilterGate {
-    bool on;  // the gate is evaluated (false: every event updates)
-    T thr;
-};
-template <typename T>
-__device__ __forceinline__ FilterGate<T> gate_of(const double* thresholds, int64_t f) {
-    const double t = thresholds[f];
-    // -inf is "always update": the gate is not evaluated; +inf and NaN fail every comparison
-    return FilterGate<T>{t != -__builtin_inf(), T(t)};
-}
-
 template <typename T, class M, bool CUSTOM, bool GATES = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void ref_events_kernel(const RefArgs a) {
     const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -587,1414 +195,6 @@ __global__ __launch_bounds__(kBlock) void ref_reset_kernel(const RefArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// Chain-parallel variant of ref_events_kernel for few filters (a single drive log): one lane
-// per axis chain, kGroup lanes per filter.  Without the adaptive gate the chains are
-// independent filters sharing an event stream, so a filter's per-event instruction stream
-// shrinks to one chain's; the log-determinant (and the gate) is the sum of the chains' logs
-// over the lane group (xor shuffles).  Every lane runs a 3-state chain: an (att, rate) chain
-// carries an inert third state (F couples nothing to it, Q = 0; its IMU row measures z = 0
-// with R = 1 and is reset after each update), so pva and aw lanes execute the same code.
-// The arithmetic per chain is the lane kernel's, operation for operation (the extra terms are
-// exact zeros); only the logdet is summed per chain instead of multiplied then logged.
-// ------------------------------------------------------------------------------------
-constexpr int kGroup = 8;
-#ifndef KF_CHAIN_DEPTH
-#define KF_CHAIN_DEPTH 2
-#endif
-constexpr int kChainDepth = KF_CHAIN_DEPTH;  // input ring of ref_chain_kernel
-#ifndef KF_STREAM_DEPTH
-#define KF_STREAM_DEPTH 8
-#endif
-constexpr int kStreamDepth = KF_STREAM_DEPTH;  // its input ring in stream mode (kf_run_stream)
-#ifndef KF_STREAM_VAR_DEPTH
-#define KF_STREAM_VAR_DEPTH 4
-#endif
-// the map pass's ring (4 state variants per lane): shallower, so the lane fits 2 waves per SIMD
-constexpr int kStreamVarDepth = KF_STREAM_VAR_DEPTH;
-#ifndef KF_STREAM_LD_BATCH
-#define KF_STREAM_LD_BATCH 1
-#endif
-// the map pass's log-det records: the group's determinant product per event, kept by lane
-// (event mod 8) and logged every 8 events (one log per lane-8-events instead of per lane-event;
-// the pass is bound by its instruction issue).  0: every lane logs its chain every event and the
-// group sums the logs (the NV = 1 chain kernel's form)
-constexpr bool kStreamLdBatch = KF_STREAM_LD_BATCH != 0;
-#ifndef KF_STREAM_RECORD_PAIRS
-#define KF_STREAM_RECORD_PAIRS 1
-#endif
-// the records from the map pass two entries per thread (stream_records2_kernel; 0: one each)
-constexpr bool kStreamRecordPairs = KF_STREAM_RECORD_PAIRS != 0;
-#ifndef KF_STREAM_VAR_SPLIT
-#define KF_STREAM_VAR_SPLIT 0
-#endif
-// the map pass's four state variants as two per lane over two 8-lane groups per chunk (variants
-// 0, 1 and 2, 3): twice the waves, each lane's event a little shorter (the covariance work
-// repeated in both groups).  Measured slower on config 1, 0.2196 vs 0.2045 ms per log in-process
-// (profiles/r04_pmc/cfg1_diag/ab_split_sym_halves.log), so off; kept for A/B builds
-constexpr bool kStreamVarSplit = KF_STREAM_VAR_SPLIT != 0;
-// lanes per filter of ref_chain_kernel
-template <int NV>
-__host__ __device__ constexpr int chain_lanes() {
-    return NV == 4 && kStreamVarSplit ? 2 * 8 : 8;
-}
-
-// Sums / ORs over the 8-lane group with DPP (a VALU-latency lane exchange, no LDS round trip):
-// quad_perm [1,0,3,2] (xor 1), quad_perm [2,3,0,1] (xor 2), then row_half_mirror (lane i <-> 7-i
-// within each 8 lanes), which pairs the two quads.  Every lane of the group ends with the total.
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141;
-constexpr int kDppRowRor8 = 0x128;  // row_ror:8: lane l of a 16-lane row reads lane l +- 8
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const v2u u = __builtin_bit_cast(v2u, v);
-    v2u r;
-    r.x = __builtin_amdgcn_mov_dpp(int(u.x), CTRL, 0xF, 0xF, false);
-    r.y = __builtin_amdgcn_mov_dpp(int(u.y), CTRL, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, r);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_d(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-
-template <typename T>
-__device__ __forceinline__ T group_sum(T v) {
-    v += dpp_d<kDppXor1>(v);
-    v += dpp_d<kDppXor2>(v);
-    v += dpp_d<kDppHalfMirror>(v);
-    return v;
-}
-
-__device__ __forceinline__ bool group_any(bool b) {
-    int v = b ? 1 : 0;
-    v |= __builtin_amdgcn_mov_dpp(v, kDppXor1, 0xF, 0xF, false);
-    v |= __builtin_amdgcn_mov_dpp(v, kDppXor2, 0xF, 0xF, false);
-    v |= __builtin_amdgcn_mov_dpp(v, kDppHalfMirror, 0xF, 0xF, false);
-    return v != 0;
-}
-
-template <typename T>
-__device__ __forceinline__ T chain_log_det(const T (&P)[6]) {
-    // one 3-state chain's log det (an aw chain's inert third state has variance 1, no coupling)
-    T num = T(1), den = T(1);
-    int ex = 0;
-    bool ok = true;
-    det3_scaled<T>(P, num, den, ok);
-    T prod = num * rcp_nr<kRefNewton>(den);
-    renorm(prod, ex);
-    const T ld = log_mant(prod, ex);
-    return ok ? ld : quiet_nan<T>();
-}
-
-// chain_log_det before its log: the determinant as a mantissa in [0.5, 1) (NaN unless the
-// block is positive definite) and a binary exponent
-template <typename T>
-__device__ __forceinline__ void chain_det_mant(const T (&P)[6], T& m, int& ex) {
-    T num = T(1), den = T(1);
-    bool ok = true;
-    det3_scaled<T>(P, num, den, ok);
-    m = num * rcp_nr<kRefNewton>(den);
-    ex = 0;
-    renorm(m, ex);
-    m = ok ? m : quiet_nan<T>();
-}
-
-// (mantissa, exponent) product over the 8-lane group, the same DPP pattern as group_sum: every
-// lane ends with the same bits (each step multiplies a pair in both orders, and x * y == y * x)
-template <typename T>
-__device__ __forceinline__ void group_prod(T& m, int& ex) {
-    m *= dpp_d<kDppXor1>(m);
-    ex += __builtin_amdgcn_mov_dpp(ex, kDppXor1, 0xF, 0xF, false);
-    m *= dpp_d<kDppXor2>(m);
-    ex += __builtin_amdgcn_mov_dpp(ex, kDppXor2, 0xF, 0xF, false);
-    m *= dpp_d<kDppHalfMirror>(m);
-    ex += __builtin_amdgcn_mov_dpp(ex, kDppHalfMirror, 0xF, 0xF, false);
-}
-
-// non-negative doubles (and +NaN) order as their bit patterns: atomic max via uint64
-__device__ __forceinline__ void atomic_max_pos(double* p, double v) {
-    if (!(v >= 0.0)) v = __builtin_nan("");
-    atomicMax(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v));
-}
-
-// The adaptive gate logdet(P_pred) > threshold (kf_workers.py:1023-1025) of the chain kernel,
-// decided on the group's determinant product (mantissa, binary exponent) against
-// exp(threshold) (1 -+ eps); only inside that band are the logs taken, as
-// group_sum(chain_log_det) > threshold, so every decision is the logs' (eps far above the logs'
-// and the products' rounding: 1e-10 in f64, 1e-4 in f32).  The log is the longest part of a
-// gated event's dependent chain, and a gated filter with few updates runs little else.
-// Non-finite or huge thresholds take the logs every event.
-template <typename T>
-struct GateBand {
-    T lo_m = T(0), hi_m = T(0);
-    int lo_e = 0, hi_e = 0;
-    bool banded = false;
-    __device__ __forceinline__ void init(double thr) {
-        banded = thr == thr && thr > -1e6 && thr < 1e6;
-        if (!banded) return;
-        const double eps = sizeof(T) == 8 ? 1e-10 : 1e-4;
-        const double k = floor(thr * 1.4426950408889634);  // exp(thr) = 2^k exp(r), r in [0, ln 2)
-        const double r = thr - k * 0.6931471805599453;
-        int e1, e2;
-        const double lo = frexp(exp(r) * (1.0 - eps), &e1), hi = frexp(exp(r) * (1.0 + eps), &e2);
-        lo_m = T(lo);
-        hi_m = T(hi);
-        lo_e = int(k) + e1;
-        hi_e = int(k) + e2;
-    }
-    // the gate for this lane's chain covariance P (live: a chain lane of the group)
-    __device__ __forceinline__ bool open(const T (&P)[6], bool live, T thr) const {
-        if (banded) {
-            T m;
-            int ex;
-            chain_det_mant(P, m, ex);
-            m = live ? m : T(1);
-            ex = live ? ex : 0;
-            group_prod(m, ex);
-            int e;
-            m = frexp(m, &e);
-            ex += e;
-            if (!(m > T(0))) return false;                           // NaN (a failed block) or 0: log -inf
-            if (ex < lo_e || (ex == lo_e && m < lo_m)) return false;  // the logs' sum below thr
-            if (ex > hi_e || (ex == hi_e && m > hi_m)) return true;   // above
-        }
-        return group_sum(live ? chain_log_det(P) : T(0)) > thr;
-    }
-};
-
-// Inputs of one event for one lane.
-template <typename T>
-struct ChainIn {
-    int type;
-    double dt;
-    T va, vb;
-};
-
-// A scored sweep's event (ref_sweep_kernel's SCORE): the track row too, the lane's own column first
-template <typename T>
-struct ChainInScored : ChainIn<T> {
-    double track[3];
-};
-
-// What one lane of a scored sweep accumulates for its own chain, in event order: the NIS terms
-// and the position error in double, and det S as a running (mantissa, exponent) product of the
-// pivots in double, renormalised every update (a relative rounding per pivot, so the log taken
-// once at the end is off by about 1e-16 per pivot whatever the sum's size; a log per update
-// would add a rounding of the running sum each time, and ~25 VALU operations).  Branch-free and
-// the same code on every lane: a lane without a chain accumulates what nobody reads, and an aw
-// lane's inert third state, whose innovation is exactly 0 and whose pivot is exactly 1 + 1, adds
-// 0 to the NIS and 1 to the exponent per IMU update, which the final log takes back (exactly).
-struct ScoreAcc {
-    int32_t ngps = 0;               // applied GPS updates (the same in every lane of a group)
-    double nis[2] = {0.0, 0.0};     // this chain's sum of w_a^2 / d_a: GPS, IMU
-    double ldm[2] = {1.0, 1.0};     // this chain's pivot product, mantissa ...
-    int32_t lde[2] = {0, 0};        // ... and binary exponent
-    int32_t npos = 0;               // events scored against the track
-    double sse = 0.0;               // this axis' sum of (x - track)^2
-
-    // one applied update of this lane's chain
-    template <typename T, int M>
-    __device__ __forceinline__ void add(int kind, const Innov<T, M>& in) {
-        double m = ldm[kind];
-#pragma unroll
-        for (int a = 0; a < M; ++a) m *= double(in.d[a]);
-        nis[kind] += double(in.nis);
-        ldm[kind] = m;
-        renorm(ldm[kind], lde[kind]);
-    }
-};
-
-// Column f of a parameter sweep's constants table [2 N + NP][B] (SweepArgs::consts)
-struct ConstsColumn {
-    const double* table;
-    int64_t B, f;
-};
-
-// One lane of the 8-lanes-per-filter kernels (ref_chain_kernel, ref_sweep_kernel,
-// ref_chain_gated_kernel): which chain lane c of a group runs, where that chain's states, block
-// rows and payload columns are, its noise constants, and the event all three kernels run.  The
-// kernels keep their own address tables (state banks, record rows, stream columns).
-template <typename T, class M, bool CUSTOM>
-struct ChainLane {
-    int c;       // lane of the group
-    bool pva;    // a (pos, vel, acc) chain; otherwise an (att, rate) chain or none
-    bool live;   // the lane holds a chain
-    int ca;      // the chain's axis among its kind
-    int xi[3];   // state indices (-1: none)
-    int pr[6];   // block-packed covariance rows (-1: none)
-    int ia, ib;  // payload columns: GPS position / IMU attitude, IMU acceleration / rate
-    T q[3], Rimu[6], Rgps;
-
-    __device__ __forceinline__ ChainLane(int lane, const RefConsts* kc)
-        : c(lane), pva(lane < M::NP), live(lane < M::NP + M::NA), ca(pva ? lane : (live ? lane - M::NP : 0)) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xi[k] = !live ? -1 : pva ? M::pva(ca, k) : (k < 2 ? M::aw(ca, k) : -1);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int aw_row = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : -1;  // (tt tw ww) of the 3x3 packing
-            pr[k] = !live ? -1 : pva ? 6 * ca + k : (aw_row < 0 ? -1 : 6 * M::NP + 3 * ca + aw_row);
-        }
-        ia = pva ? ca : M::imu_att(ca);
-        ib = pva ? M::imu_acc(ca) : M::imu_rate(ca);
-        q[0] = T(pva ? kQPos : kQAtt), q[1] = T(pva ? kQVel : kQRate), q[2] = T(pva ? kQAcc : 0.0);
-        Rimu[0] = T(pva ? kRPos : kRAtt), Rimu[3] = T(pva ? kRVel : kRRate), Rimu[5] = T(pva ? kRAcc : 1.0);
-        Rimu[1] = Rimu[2] = Rimu[4] = T(0);
-        Rgps = T(kRGps);
-        if constexpr (CUSTOM) {  // this lane's chain states (the inert third state of an aw lane keeps 0 / 1)
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (xi[k] >= 0) {
-                    q[k] = T(ro(kc)->q[xi[k]]);
-                    Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(kc)->r_imu[xi[k]]);
-                }
-            if (pva) Rgps = T(ro(kc)->r_gps[ca]);
-        }
-    }
-
-    // The lane of filter f of a parameter sweep (ref_sweep_kernel's PARAMS): its chain's constants
-    // from column f of the table consts [2 N + NP][B] (rows: q per state, r_imu per state, r_gps
-    // per axis), converted as the CUSTOM constants are.  Plain per-lane vector loads, every one in
-    // bounds: a lane without the state reads row 0 of the section and keeps the literal (an aw
-    // lane's inert third state: Q = 0, R = 1).
-    __device__ __forceinline__ ChainLane(int lane, const ConstsColumn& col)
-        : ChainLane(lane, static_cast<const RefConsts*>(nullptr)) {
-        static_assert(!CUSTOM, "the table replaces the handle's constants");
-        const double* consts = col.table;
-        const int64_t B = col.B, f = col.f;
-        double tq[3], tr[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int row = xi[k] >= 0 ? xi[k] : 0;
-            tq[k] = consts[int64_t(row) * B + f];
-            tr[k] = consts[int64_t(M::N + row) * B + f];
-        }
-        const double tg = consts[int64_t(2 * M::N + (pva ? ca : 0)) * B + f];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (xi[k] >= 0) {
-                q[k] = T(tq[k]);
-                Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(tr[k]);
-            }
-        if (pva) Rgps = T(tg);
-    }
-
-    // P[k] where the lane holds no row k: the identity (an aw lane's inert state has variance 1)
-    static __device__ __forceinline__ T unit(int k) { return T(k == 0 || k == 3 || k == 5 ? 1 : 0); }
-
-    // event's predict, line for line, for ref_smooth_kernel: x = F x for the NL states, P = F P F^T
-    // + Q dt, F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane), the same
-    // operations in the same order, so its P is event's P_pred bit for bit.  FP leaves with F P of
-    // the covariance that came in (the smoother gain reads it).  event keeps its own copy of these
-    // lines: calling this member from it compiled every chain-layout kernel to another instruction
-    // stream (profiles/rts_smoother/isa_compare_predict_member.log).  Change both together.
-    template <int NL>
-    __device__ __forceinline__ void predict(T dt, T (&x)[NL][3], T (&P)[6], T (&FP)[3][3]) const {
-        const T c02 = pva ? T(0.5) * dt * dt : T(0);
-        const T c12 = pva ? dt : T(0);
-#pragma unroll
-        for (int v = 0; v < NL; ++v) {
-            const T xn0 = fmaT(c02, x[v][2], fmaT(dt, x[v][1], x[v][0]));
-            const T xn1 = fmaT(c12, x[v][2], x[v][1]);
-            x[v][0] = xn0;
-            x[v][1] = xn1;
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
-            FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
-            FP[2][j] = P[tri<3>(2, j)];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                T s = FP[i][j];
-                if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
-                if (j == 1) s = fmaT(FP[i][2], c12, s);
-                P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
-            }
-    }
-
-    // One event on this lane's chain, for NL states that share the covariance: predict, the
-    // adaptive gate (gated: against thr, through the group's GateBand), the GPS / IMU update,
-    // the aw lane's inert-state reset, and NaN poisoning of the whole group when any of its chains
-    // failed (st then kNotSpd).  Returns whether the update was applied; every lane of the group
-    // must call it together (the gate and the poisoning exchange over the group).
-    // SCORE (a scored sweep): an applied update also adds its chain's innovation statistics to *sc
-    // (sel_update_nv's INNOV: the y, L and pivots of the update that runs anyway).
-    template <int NL, bool SCORE = false>
-    __device__ __forceinline__ bool event(int type, T dt, T va, T vb, bool gated, const GateBand<T>& gate, T thr,
-                                          T (&x)[NL][3], T (&P)[6], int32_t& st, ScoreAcc* sc = nullptr) const {
-        if (type == 255) return false;
-        // predict: F = [[1, dt, c02], [0, 1, c12], [0, 0, 1]] (c02 = c12 = 0 on an aw lane)
-        const T c02 = pva ? T(0.5) * dt * dt : T(0);
-        const T c12 = pva ? dt : T(0);
-#pragma unroll
-        for (int v = 0; v < NL; ++v) {
-            const T xn0 = fmaT(c02, x[v][2], fmaT(dt, x[v][1], x[v][0]));
-            const T xn1 = fmaT(c12, x[v][2], x[v][1]);
-            x[v][0] = xn0;
-            x[v][1] = xn1;
-        }
-        T FP[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            FP[0][j] = fmaT(c02, P[tri<3>(2, j)], fmaT(dt, P[tri<3>(1, j)], P[tri<3>(0, j)]));
-            FP[1][j] = fmaT(c12, P[tri<3>(2, j)], P[tri<3>(1, j)]);
-            FP[2][j] = P[tri<3>(2, j)];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                T s = FP[i][j];
-                if (j == 0) s = fmaT(FP[i][2], c02, fmaT(FP[i][1], dt, s));
-                if (j == 1) s = fmaT(FP[i][2], c12, s);
-                P[tri<3>(i, j)] = (i == j) ? s + q[i] * dt : s;
-            }
-        bool applied = (type == kGps || type == kImu);
-        if (gated && applied) applied = gate.open(P, live, thr);
-        bool ok = true;
-        if (applied) {
-            if (type == kGps) {
-                if (pva) {
-                    T zb[NL][1];
-#pragma unroll
-                    for (int v = 0; v < NL; ++v) zb[v][0] = va;
-                    const T R[1] = {Rgps};
-                    if constexpr (SCORE) {
-                        Innov<T, 1> inn;
-                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR, true>(
-                            x, P, zb, R, &inn);
-                        sc->add(0, inn);
-                    } else {
-                        ok = sel_update_nv<3, 1, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, R);
-                    }
-                }
-                if constexpr (SCORE) sc->ngps += 1;
-            } else {
-                T zb[NL][3];
-#pragma unroll
-                for (int v = 0; v < NL; ++v) {
-                    const T V = fmaT(vb, dt, x[v][1]);
-                    const T X = fmaT(V, dt, x[v][0]);
-                    zb[v][0] = pva ? X : va;
-                    zb[v][1] = pva ? V : vb;
-                    zb[v][2] = pva ? vb : T(0);
-                }
-                if constexpr (SCORE) {
-                    Innov<T, 3> inn;
-                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR, true>(
-                        x, P, zb, Rimu, &inn);
-                    sc->add(1, inn);
-                } else {
-                    ok = sel_update_nv<3, 3, true, T, kRefNewton, true, NL, kRefJoseph<T>, kRefGainR>(x, P, zb, Rimu);
-                }
-                if (!pva) {  // reset the inert state
-#pragma unroll
-                    for (int v = 0; v < NL; ++v) x[v][2] = T(0);
-                    P[5] = T(1);
-                }
-            }
-        }
-        if (group_any(!ok)) {
-            st = kNotSpd;
-#pragma unroll
-            for (int v = 0; v < NL; ++v)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) x[v][k] = quiet_nan<T>();
-#pragma unroll
-            for (int k = 0; k < 6; ++k) P[k] = quiet_nan<T>();
-        }
-        return applied;
-    }
-};
-
-// The input ring of the chain-layout kernels: event t's inputs are loaded D - 1 events ahead
-// through a fully unrolled ring of named buffers (static indices, no loop-carried copies).
-// load(t, in) is called for t up to n + D - 2 and clamps past-the-end events itself (they re-read
-// a last event); the prologue's loads are drained once, so no in-loop wait targets them (vmcnt
-// counts in order: the step's wait for its own buffer then leaves the D - 1 younger loads in
-// flight).  Each depth adds a copy of the event body (48 KB of code at 8).  Depths 2, 3, 4 and 8
-// were A/B-measured on config 1 (one filter, per-filter layout) without a resolvable difference: a
-// single wave's launch time varies +-10% from launch to launch
-// (profiles/r01_ab/chain_depth_inproc.json), so that default stays at 2.  Stream mode gathers
-// each filter's events from its own part of the stream (a cache line per 1.8 events, lines differ
-// per filter), so its loads see HBM latency: a deeper ring.
-template <int D, typename T, class In = ChainIn<T>, class Load, class Step>
-__device__ __forceinline__ void ring_run(int n, Load&& load, Step&& step) {
-    if (n <= 0) return;
-    In buf[D];
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j) load(j, buf[j]);
-    __builtin_amdgcn_s_waitcnt(0);
-    int t = 0;
-    for (; t + D <= n; t += D) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            load(t + j + D - 1, buf[(j + D - 1) % D]);
-            step(t + j, buf[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j)
-        if (t + j < n) step(t + j, buf[j]);
-}
-
-// NV > 1 (stream mode only): NV variants of each filter that differ only in their start state
-// (kf_run_stream's map pass: a chunk from its guess and from the guess + delta on each chain
-// component) share one lane.  The covariance recursion does not read the state, so P, S and K
-// are computed once per event and every variant's state is updated with them (ChainLane::event's
-// NL states through sel_update_nv).  Variant v's state is
-// column v * B + f of a state bank of NV * B columns (the covariance: column f), and its
-// trajectory records go to rows v * s_vstride.
-// GATES (kf_run_events_gates, per-filter layout): each 8-lane group gates its filter by its own
-// a.thresholds[f], its GateBand set from it as ref_sweep_kernel's groups do.
-template <typename T, class M, bool STREAM, bool CUSTOM, int NV = 1, bool GATES = false>
-__global__ __launch_bounds__(kBlock) void ref_chain_kernel(const RefArgs a) {
-    static_assert(NV == 1 || STREAM, "state variants are a stream-mode feature");
-    static_assert(!GATES || (!STREAM && NV == 1), "per-filter gates are a per-filter-layout feature");
-    if (a.skip && *a.skip) return;  // the sequential fallback of a stream run that passed its checks
-    constexpr int LPF = chain_lanes<NV>();         // lanes per filter
-    constexpr int NL = LPF == 2 * kGroup ? 2 : NV;  // variants this lane holds
-    const int64_t g = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t f = g / LPF;
-    if (f >= a.B) return;  // whole groups leave together (LPF divides the wave)
-    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), a.kc);
-    const int c = L.c;
-    const bool pva = L.pva, live = L.live;
-    const auto& xi = L.xi;
-    const auto& pr = L.pr;
-    const int vb = NL < NV ? int((g % LPF) / kGroup) * NL : 0;  // this lane's first variant
-    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
-    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
-    const uint32_t rbank = uint32_t(NV) * rb;  // row stride of the state / covariance bank
-    const uint32_t rb8 = uint32_t(a.B) * 8u;
-    const uint32_t off8 = uint32_t(f) * 8u;
-    // this lane's state and block rows as voffsets into row spans
-    uint32_t vx[3], vp[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vx[k] = xi[k] >= 0 ? uint32_t(xi[k]) * rbank + off : kDropOffset;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vp[k] = pr[k] >= 0 ? uint32_t(pr[k]) * rbank + off : kDropOffset;
-    const uint32_t v_tr = (xi[0] >= 0 && xi[0] < M::NTRAJ) ? uint32_t(xi[0]) * rb + off : kDropOffset;
-    const uint32_t v_ld = c == 0 ? off : kDropOffset;
-    const uint32_t v_a = uint32_t(L.ia) * rb + off, v_b = uint32_t(L.ib) * rb + off;
-
-    T x[NL][3], P[6];
-    T xs0[3];  // variant 0's start (the map pass's guess)
-    {
-        const auto rx = span_rsrc(a.x, 0, rbank, M::N), rp = span_rsrc(a.P, 0, rbank, M::NBLK);
-#pragma unroll
-        for (int v = 0; v < NL; ++v)
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                x[v][k] = ldv(rx, vx[k] == kDropOffset ? kDropOffset : vx[k] + uint32_t(vb + v) * rb, T(0));
-#pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
-        if constexpr (NL < NV) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) xs0[k] = ldv(rx, vx[k], T(0));
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) xs0[k] = x[0][k];
-        }
-    }
-    // the map pass's seam check reads the next chunk's start covariance: loaded here, before
-    // any of this lane's stores (a later load would wait for all of them, vmcnt being in order)
-    double wnx[6] = {0, 0, 0, 0, 0, 0};
-    if constexpr (NV == 4) {
-        if (live && a.s_maps && a.s_check && f + 1 < a.B) {
-            const T* wn = static_cast<const T*>(a.s_wnext);
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (pr[k] >= 0) wnx[k] = double(wn[int64_t(pr[k]) * a.B + f + 1]);
-        }
-    }
-    int32_t st = a.status[f];
-    const bool need_ld = a.logdet != nullptr;
-    FilterGate<T> fg{a.gate != 0, T(a.threshold)};  // the launch's gate, or GATES: the filter's own
-    if constexpr (GATES) fg = gate_of<T>(a.thresholds, f);
-    GateBand<T> gate;
-    if (fg.on) gate.init(GATES ? a.thresholds[f] : a.threshold);
-    constexpr bool kLdBatch = STREAM && NV == 4 && kStreamLdBatch;
-    T bm = T(1);  // kLdBatch: the group's determinant product of event (t - t mod 8 + c)
-    int bex = 0;
-
-    // stream mode: this filter's event t is stream event e0 + t; one descriptor per stream
-    // (events outside [0, S) are skipped: dropped loads, NONE type, dropped records)
-    const int64_t e0 = STREAM ? (f % a.s_nchunks) * a.s_chunk + a.s_shift : 0;
-    const uint32_t S = STREAM ? uint32_t(a.s_len) : 0u;
-    const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
-    const auto r_pay = bytes_rsrc(a.payload, S * 9u * uint32_t(sizeof(T)));
-    // filter f is variant f / s_nchunks of its chunk (NV = 1) or carries variants 0 .. NV - 1:
-    // with s_nvar > 1, variant q's trajectory records go to rows [q * s_vstride, q * s_vstride +
-    // S) (s_vstride >= S + chunk, so a padded chunk's rows past S stay inside its own variant),
-    // and only variant 0 writes the others
-    const int var = STREAM ? int(f / a.s_nchunks) + vb : 0;
-    const uint32_t trows = STREAM ? (a.s_nvar > 1 ? uint32_t(a.s_nvar) * uint32_t(a.s_vstride) : S) : 0u;
-    const auto r_str = bytes_rsrc(a.traj, trows * uint32_t(M::NTRAJ * sizeof(T)));
-    const auto r_scv = bytes_rsrc(a.cov, S * uint32_t(M::NBLK * sizeof(T)));
-    const auto r_sld = bytes_rsrc(a.logdet, S * uint32_t(sizeof(T)));
-    const auto r_sup = bytes_rsrc(a.updated, S);
-    // Stream offsets are plain 32-bit products of ue = uint32(e): an event before the stream
-    // start wraps far past every descriptor's length and one past its end lands beyond it, so
-    // loads return 0 and stores drop without a select on the address (a select there was turned
-    // into branches around the loads, whose joins drained the prefetch ring with vmcnt(0)).
-    // Lanes without a record OR in bit 31 (kf_run_stream keeps (S + W) * rows * w < 2^31).
-    const uint32_t m_tr = v_tr != kDropOffset ? 0u : kDropOffset;
-    const uint32_t col_tr = v_tr != kDropOffset ? (uint32_t(var) * uint32_t(a.s_vstride) * M::NTRAJ + uint32_t(xi[0])) *
-                                                      uint32_t(sizeof(T))
-                                                : 0u;
-    const uint32_t vstep_tr = uint32_t(a.s_vstride) * uint32_t(M::NTRAJ * sizeof(T));  // next variant's rows
-    const uint32_t m_ld = c == 0 && var == 0 ? 0u : kDropOffset;  // variant 0's group only
-    uint32_t col_cv[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        col_cv[k] = pr[k] >= 0 && var == 0 ? uint32_t(pr[k]) * uint32_t(sizeof(T)) : kDropOffset;
-    auto load = [&](int t, ChainIn<T>& in) {
-        if constexpr (STREAM) {
-            const uint32_t ue = uint32_t(e0 + t);
-            const int ty = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue, 0, 0));
-            in.type = ue < S ? ty : 255;
-            in.dt = ldv(r_dt, ue * 8u, 0.0);
-            in.va = ldv(r_pay, (ue * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T)), T(0));
-            in.vb = ldv(r_pay, (ue * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T)), T(0));
-        } else {
-            in.type = int(ldb<uint8_t>(a.etype, t, uint32_t(a.B), uint32_t(f)));
-            in.dt = ldb<double>(a.dt, t, rb8, off8);
-            const auto rpay = span_rsrc(a.payload, int64_t(t) * 9, rb, 9);
-            in.va = ldv(rpay, v_a, T(0));
-            in.vb = ldv(rpay, v_b, T(0));
-        }
-    };
-    auto step = [&](int t, const ChainIn<T>& in) {
-        const bool applied = L.event(in.type, T(in.dt), in.va, in.vb, fg.on, gate, fg.thr, x, P, st);
-        if constexpr (STREAM) {
-            const uint32_t ue = uint32_t(e0 + t);
-#pragma unroll
-            for (int v = 0; v < NL; ++v)
-                stv(r_str, (ue * uint32_t(M::NTRAJ * sizeof(T)) + col_tr + uint32_t(v) * vstep_tr) | m_tr, x[v][0]);
-            // absent records: skipped by a wave-uniform branch (a store to a zero-length
-            // descriptor is dropped, but it is still issued)
-            if (a.cov) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k)
-                    stv(r_scv, (ue * uint32_t(M::NBLK * sizeof(T)) + col_cv[k]) | (col_cv[k] & kDropOffset), P[k]);
-            }
-            if (need_ld) {
-                if constexpr (kLdBatch) {
-                    T m;
-                    int ex;
-                    chain_det_mant(P, m, ex);
-                    m = live ? m : T(1);
-                    ex = live ? ex : 0;
-                    group_prod(m, ex);
-                    const int slot = t & (kGroup - 1);
-                    if (c == slot) {
-                        bm = m;
-                        bex = ex;
-                    }
-                    if (slot == kGroup - 1 || t == a.T - 1) {  // wave-uniform: lane j logs event t - slot + j
-                        int e;
-                        const T ld = log_mant(frexp(bm, &e), bex + e);
-                        const bool mine = c <= slot;
-                        if (group_any(mine && !(ld == ld))) st = kNotSpd;
-                        const uint32_t uj = uint32_t(e0 + t - slot + c);
-                        stv(r_sld, (uj * uint32_t(sizeof(T))) | (mine && var == 0 ? 0u : kDropOffset), ld);
-                    }
-                } else {
-                    const T ld = group_sum(live ? chain_log_det(P) : T(0));
-                    st = (ld == ld) ? st : kNotSpd;
-                    stv(r_sld, (ue * uint32_t(sizeof(T))) | m_ld, ld);
-                }
-            }
-            if (a.updated) __builtin_amdgcn_raw_buffer_store_b8(applied ? uint8_t(1) : uint8_t(0), r_sup, ue | m_ld, 0, 0);
-        } else {
-            stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, x[0][0]);
-            {
-                const auto rc = span_rsrc(a.cov, int64_t(t) * M::NBLK, rb, M::NBLK);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) stv(rc, vp[k], P[k]);
-            }
-            if (need_ld) {
-                const T ld = group_sum(live ? chain_log_det(P) : T(0));
-                st = (ld == ld) ? st : kNotSpd;
-                stv(span_rsrc(a.logdet, t, rb, 1), v_ld, ld);
-            }
-            if (a.updated && c == 0) a.updated[int64_t(t) * a.B + f] = applied ? 1 : 0;
-        }
-    };
-
-    constexpr int D = STREAM ? (NV > 1 ? kStreamVarDepth : kStreamDepth) : kChainDepth;
-    const int T_ = a.T;
-    ring_run<D, T>(T_, [&](int t, ChainIn<T>& in) { load(t < T_ ? t : T_ - 1, in); }, step);
-    {
-        const auto rx = span_rsrc(a.x, 0, rbank, M::N), rp = span_rsrc(a.P, 0, rbank, M::NBLK);
-#pragma unroll
-        for (int v = 0; v < NL; ++v)
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                stv(rx, vx[k] == kDropOffset ? kDropOffset : vx[k] + uint32_t(vb + v) * rb, x[v][k]);
-        if (vb == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) stv(rp, vp[k], P[k]);
-        }
-    }
-    if (c == 0 && vb == 0) a.status[f] = st;
-    if constexpr (NV == 4) {
-        // the map pass's epilogue (kf_run_stream): this chunk's affine map per chain, x_end =
-        // A x_start + b (fp64), A by differences of the variants (variant q + 1 started at the
-        // guess + delta on component q), b = x_end(guess) - A guess; then the covariance seam:
-        // this chunk's end covariance against the next chunk's start covariance, relative to
-        // the end covariance's largest entry in the chain (one atomic per wave)
-        constexpr int NCH = M::NP + M::NA;
-        const int ns = pva ? 3 : 2;
-        double crel = 0.0;
-        // every variant's end state: with the split, variants 2, 3 come from the other group of
-        // 16 (DPP row_ror:8 pairs lane l with l + 8 within the row), every lane exchanging
-        double xe[4][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-            for (int v = 0; v < NL; ++v) xe[v][k] = double(x[v][k]);
-            if constexpr (NL < 4) {
-#pragma unroll
-                for (int v = 0; v < NL; ++v) xe[NL + v][k] = dpp_d<kDppRowRor8>(xe[v][k]);
-            }
-        }
-        if (live && a.s_maps && vb == 0) {
-            double A[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, b[3] = {0, 0, 0};
-            const double rdelta = 1.0 / a.s_delta;  // delta is a power of two: exact
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (k >= ns) continue;
-                const double e0v = xe[0][k];
-                double sacc = e0v;
-#pragma unroll
-                for (int qq = 0; qq < 3; ++qq) {
-                    if (qq >= ns) continue;
-                    A[k][qq] = (xe[qq + 1][k] - e0v) * rdelta;
-                    sacc = __builtin_fma(-A[k][qq], double(xs0[qq]), sacc);
-                }
-                b[k] = sacc;
-            }
-            double* mo = a.s_maps + (f * NCH + c) * 12;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-#pragma unroll
-                for (int qq = 0; qq < 3; ++qq) mo[k * 3 + qq] = A[k][qq];
-                mo[9 + k] = b[k];
-            }
-            if (a.s_check && f + 1 < a.B) {
-                double scale = 0.0, gap = 0.0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    if (pr[k] < 0) continue;
-                    const double pe = double(P[k]);
-                    scale = fmax(scale, fabs(pe));
-                    gap = fmax(gap, fabs(pe - wnx[k]));
-                }
-                const double rel = gap / fmax(scale, 1e-300);
-                crel = rel == rel ? rel : __builtin_inf();
-            }
-        }
-        if (a.s_check) {
-            // the wave's max over its chunks (DPP inside a group; lanes of finished groups hold
-            // 0), one atomic per wave: every chunk's lanes finish together, and one atomic per
-            // chunk on the same address queued up behind each other at the end of the pass
-            crel = fmax(crel, dpp_d<kDppXor1>(crel));
-            crel = fmax(crel, dpp_d<kDppXor2>(crel));
-            crel = fmax(crel, dpp_d<kDppHalfMirror>(crel));
-            // a wave whose chunks all exist has every lane here (a partial last wave lost its
-            // dead groups at the top, so it keeps one atomic per chunk)
-            const bool full = (g & ~int64_t(63)) / LPF + 64 / LPF <= a.B;  // wave-uniform
-            if (full) {
-#pragma unroll
-                for (int sh = kGroup; sh < 64; sh <<= 1) crel = fmax(crel, __shfl_xor(crel, sh, 64));
-                const bool lane0 = (threadIdx.x & 63) == 0;
-                if (lane0 && crel != 0.0) atomic_max_pos(&a.s_check->cov_gap, crel);
-                const bool any_bad = __builtin_amdgcn_ballot_w64(c == 0 && st != 0) != 0;
-                if (lane0 && any_bad) atomicOr(&a.s_check->bad, kStreamBadFilter);
-            } else {
-                if (c == 0 && vb == 0 && crel != 0.0) atomic_max_pos(&a.s_check->cov_gap, crel);
-                if (c == 0 && vb == 0 && st != 0) atomicOr(&a.s_check->bad, kStreamBadFilter);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// Threshold sweep (kf_run_sweep): ONE event stream [T] run by B gated filters that differ only in
-// their adaptive threshold (kf_workers.py:959-1058; the experiment loop's r_value draw,
-// :2298-2317) and their start state.  The chain kernel's layout, 8 lanes per filter and lane c on
-// axis chain c, so a wave carries 8 thresholds; every group reads the same stream entries (byte
-// range descriptors as in stream mode: the 8 groups' loads hit one cache line), and the event's
-// type and dt are wave-uniform.  Each event is ChainLane::event, gated by the group's own
-// threshold.  The groups of a wave disagree about `applied`, so the wave pays the update whenever
-// one of its groups applies it: a sweep costs about what its most-updating threshold costs.  Records in kf_run_events' layouts ([T][W][B], [T][B]), an
-// update count per filter, and the handle-layout state every ckpt_every events.
-//
-// TAILS (kf_run_tails): the same groups as ragged tails of the one stream.  Group f gathers its
-// start state itself (row tails[f].src_row, column src_col of src_x / src_P, or its own handle
-// column), runs the events [lo, hi) of the stream and writes its end state to handle column f; no
-// records, no checkpoints.  The event's type and dt are the group's own, so the NONE / GPS / IMU
-// branches diverge between groups (a group is active or inactive as a whole: its DPP reductions
-// stay legal).  The wave runs to its longest tail with the finished groups predicated off, and
-// the input ring clamps per group to the tail's own last event; an empty tail loads nothing.
-//
-// PARAMS (kf_run_sweep_params): the groups differ in their noise constants as well.  Lane set-up
-// fills the lane's q / Rimu / Rgps from column f of a.consts (ChainLane's table constructor)
-// instead of the literals or the handle's scalars, once, beside the threshold and before the
-// ring's prologue, whose drain covers those loads too; a.thresholds may be null (every group
-// -inf).  Everything after set-up is the sweep's: the ring, ChainLane::event, the records.
-//
-// SCORE (kf_run_sweep_scores; PARAMS only): the run ranked where it runs.  Each lane keeps a
-// ScoreAcc for its own chain, fed in event order: an applied update adds the NIS terms and the
-// pivots that sel_update_nv's INNOV hands out of the update itself, and after every event a pva
-// lane adds its axis' squared distance to the track row, which came through the ring with the
-// event's inputs (NP more loads per event: the compiler counts the ring's in-loop vmcnt waits per
-// instantiation, and the prologue's drain is a full one).  No atomics: after the last event one
-// group_sum per row, and lane 0 stores the eight rows.  The filter's own arithmetic, records and
-// checkpoints are the PARAMS kernel's.
-// ------------------------------------------------------------------------------------
-#ifndef KF_SWEEP_DEPTH
-#define KF_SWEEP_DEPTH 4
-#endif
-constexpr int kSweepDepth = KF_SWEEP_DEPTH;  // input ring of ref_sweep_kernel
-constexpr int kSweepBlock = 64;              // one wave (8 thresholds) per workgroup: waves spread over the CUs
-
-// where group f's lanes take their constants from: the handle's, or PARAMS: column f of the table
-template <bool PARAMS>
-__device__ __forceinline__ auto sweep_consts(const SweepArgs& a, int64_t f) {
-    if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
-    else return a.kc;
-}
-
-template <typename T, class M, bool CUSTOM, bool TAILS = false, bool PARAMS = false, bool SCORE = false>
-__global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs a) {
-    static_assert(!PARAMS || (!TAILS && !CUSTOM), "per-filter constants: the plain sweep, in place of the handle's");
-    static_assert(!SCORE || PARAMS, "scores: the parameter sweep's (track and scores share the tails' slots)");
-    static_assert(consts_rows(M::N) == 2 * M::N + M::NP, "the table's rows: q, r_imu, r_gps");
-    const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
-    const int64_t f = g / kGroup;
-    // TAILS: the group's tail, and the wave's longest (every lane of the wave takes part in the
-    // reduction, the groups past B with length 0, before those leave)
-    TailSpec tl{0, 0, -1, 0};
-    int len = 0, wave_len = 0;
-    if constexpr (TAILS) {
-        if (f < a.B) {
-            tl = a.tails[f];
-            len = tl.hi - tl.lo;
-        }
-        wave_len = len;
-#pragma unroll
-        for (int sh = kGroup; sh < 64; sh <<= 1) wave_len = max(wave_len, __shfl_xor(wave_len, sh, 64));
-        wave_len = wave_uniform(wave_len);
-    }
-    if (f >= a.B) return;  // whole groups leave together
-    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), sweep_consts<PARAMS>(a, f));
-    const int c = L.c;
-    const bool live = L.live;
-    const auto& xi = L.xi;
-    const auto& pr = L.pr;
-    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
-    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
-    uint32_t vx[3], vp[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vx[k] = xi[k] >= 0 ? uint32_t(xi[k]) * rb + off : kDropOffset;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vp[k] = pr[k] >= 0 ? uint32_t(pr[k]) * rb + off : kDropOffset;
-    const uint32_t v_tr = (xi[0] >= 0 && xi[0] < M::NTRAJ) ? uint32_t(xi[0]) * rb + off : kDropOffset;
-    const uint32_t v_ld = c == 0 ? off : kDropOffset;
-    const uint32_t v_up = c == 0 ? uint32_t(f) : kDropOffset;
-
-    T x[1][3], P[6];
-    if constexpr (TAILS) {
-        // the group's own source column (64-bit addressing: row src_row of [R][rows][src_B]), or
-        // its handle column; the rows a lane does not hold keep the handle load's 0 / 1
-        const bool own = tl.src_row < 0;
-        const int64_t sb = own ? a.B : a.src_B;
-        const T* sx = own ? static_cast<const T*>(a.x) + f
-                          : static_cast<const T*>(a.src_x) + int64_t(tl.src_row) * M::N * sb + tl.src_col;
-        const T* sp = own ? static_cast<const T*>(a.P) + f
-                          : static_cast<const T*>(a.src_P) + int64_t(tl.src_row) * M::NBLK * sb + tl.src_col;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[0][k] = xi[k] >= 0 ? sx[int64_t(xi[k]) * sb] : T(0);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? sp[int64_t(pr[k]) * sb] : L.unit(k);
-    } else {
-        const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[0][k] = ldv(rx, vx[k], T(0));
-#pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
-    }
-    // a tail from a source column starts with status OK, as after kf_set_state
-    int32_t st = (TAILS && tl.src_row >= 0) ? 0 : a.status[f];
-    int32_t nup = 0;
-    // the group's threshold; NaN never opens the gate (every comparison with it is false), and
-    // -inf is "always update": the gate is not evaluated (a covariance that is not positive
-    // definite has no log-det to compare, and the reference's slogdet still passes -inf there)
-    const double thr_d = (PARAMS && !a.thresholds) ? -__builtin_inf() : a.thresholds[f];
-    const T thr = T(thr_d);
-    const bool always = thr_d == -__builtin_inf();
-    GateBand<T> gate;
-    gate.init(thr_d);
-    const bool need_tr = !TAILS && a.traj != nullptr, need_ld = !TAILS && a.logdet != nullptr;
-    const bool need_up = !TAILS && a.updated != nullptr;
-
-    const uint32_t S = uint32_t(a.T);
-    const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
-    const auto r_pay = bytes_rsrc(a.payload, S * 9u * uint32_t(sizeof(T)));
-    // stream event ue's inputs; dead = ~0u drops the loads (offset 2^32 - 1 lies past every byte
-    // range, the 4 GiB payload's too)
-    // SCORE: track row ue rides in the ring with the event's other inputs, the ring's last loads:
-    // a pva lane loads the columns the model reads, its own first (a null track: a zero-length
-    // range, loads nothing, scores nothing); the other lanes' loads are dropped (~0u lies past
-    // every byte range, 24 T < 2^32)
-    // (everything of SCORE sits under if constexpr or in a type that is empty without it: the
-    // other instantiations must stay the instruction streams they were)
-    using In = std::conditional_t<SCORE, ChainInScored<T>, ChainIn<T>>;
-    struct NoScore {};
-    std::conditional_t<SCORE, ScoreAcc, NoScore> sc;
-    auto load = [&](uint32_t ue, uint32_t dead, In& in) {
-        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, ue | dead, 0, 0));
-        in.dt = ldv(r_dt, (ue * 8u) | dead, 0.0);
-        in.va = ldv(r_pay, ((ue * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T))) | dead, T(0));
-        in.vb = ldv(r_pay, ((ue * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T))) | dead, T(0));
-        if constexpr (SCORE) {
-            const auto r_trk = bytes_rsrc(a.track, S * 24u);
-            const uint32_t m_trk = L.pva ? 0u : ~0u;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                in.track[k] = k < M::NP ? ldv(r_trk, (ue * 24u + uint32_t((L.ca + k) % M::NP) * 8u) | m_trk | dead, 0.0)
-                                        : 0.0;
-        }
-    };
-    int ck_left = TAILS ? 0 : a.ckpt_every;  // events until the next checkpoint (wave-uniform)
-    int ck_row = 0;
-    auto step = [&](int t, const In& in) {
-        // every lane of the wave loaded the same type and dt: scalars (TAILS: the group's own)
-        const int type = TAILS ? in.type : wave_uniform(in.type);
-        bool applied;
-        if constexpr (SCORE) {
-            applied = L.template event<1, true>(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st, &sc);
-            // the event's position against its track row, whatever its type: scored when every
-            // column the model reads is a number (a NaN in any of them: no reference here)
-            if (a.track != nullptr) {  // wave-uniform
-                const bool have = !(in.track[0] != in.track[0] || in.track[1] != in.track[1] ||
-                                    in.track[2] != in.track[2]);
-                const double e = have ? double(x[0][0]) - in.track[0] : 0.0;
-                sc.npos += have ? 1 : 0;
-                sc.sse = __builtin_fma(e, e, sc.sse);
-            }
-        } else {
-            applied = L.event(type, T(in.dt), in.va, in.vb, !always, gate, thr, x, P, st);
-        }
-        nup += applied ? 1 : 0;
-        // absent records: skipped by wave-uniform branches
-        if (need_tr) stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, x[0][0]);
-        if (need_ld) {
-            const T ld = group_sum(live ? chain_log_det(P) : T(0));
-            st = (ld == ld) ? st : kNotSpd;
-            stv(span_rsrc(a.logdet, t, rb, 1), v_ld, ld);
-        }
-        if (need_up)
-            __builtin_amdgcn_raw_buffer_store_b8(applied ? uint8_t(1) : uint8_t(0),
-                                                 span_rsrc(a.updated, t, uint32_t(a.B), 1), v_up, 0, 0);
-        if (ck_left > 0 && --ck_left == 0) {  // checkpoint row ck_row: the filter after this event
-            ck_left = a.ckpt_every;
-            const auto cx = span_rsrc(a.ckpt_x, int64_t(ck_row) * M::N, rb, M::N);
-            const auto cp = span_rsrc(a.ckpt_P, int64_t(ck_row) * M::NBLK, rb, M::NBLK);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) stv(cx, vx[k], x[0][k]);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) stv(cp, vp[k], P[k]);
-            ++ck_row;
-        }
-    };
-
-    if constexpr (TAILS) {
-        // the ring over the wave's longest tail (finite, wave-uniform, known before the loop): step s
-        // is the group's event lo + s, its loads clamped to the tail's own last event (so never past
-        // T - 1); a group past its tail is predicated off, and an empty tail loads nothing
-        const uint32_t dead = len > 0 ? 0u : ~0u;
-        ring_run<kSweepDepth, T>(
-            wave_len, [&](int s, ChainIn<T>& in) { load(uint32_t(tl.lo + (s < len ? s : len - 1)), dead, in); },
-            [&](int s, const ChainIn<T>& in) {
-                if (s < len) step(s, in);
-            });
-    } else {
-        const int T_ = a.T;
-        ring_run<kSweepDepth, T, In>(T_, [&](int t, In& in) { load(uint32_t(t < T_ ? t : T_ - 1), 0u, in); }, step);
-    }
-    {
-        const auto rx = span_rsrc(a.x, 0, rb, M::N), rp = span_rsrc(a.P, 0, rb, M::NBLK);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) stv(rx, vx[k], x[0][k]);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) stv(rp, vp[k], P[k]);
-    }
-    {
-        const auto rs = span_rsrc(a.status, 0, uint32_t(a.B) * 4u, 1);
-        __builtin_amdgcn_raw_buffer_store_b32(uint32_t(st), rs, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
-        if (a.n_updated) {
-            const auto rn = span_rsrc(a.n_updated, 0, uint32_t(a.B) * 4u, 1);
-            __builtin_amdgcn_raw_buffer_store_b32(uint32_t(nup), rn, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
-        }
-    }
-    if constexpr (SCORE) {
-        // the eight rows of column f: each float row one group_sum of the chains' own sums (a GPS
-        // row: the pva chains'), the logs taken here, once; NaN where the filter failed.  Lane 0
-        // stores them (row r at r B 8 + f 8 of one span; 64 B < 2^31 by the state span's limit).
-        const bool pva = L.pva;
-        const double nan = quiet_nan<double>();
-        const bool bad = st != 0;
-        double row[kScoreRows];
-        const int32_t nimu = nup - sc.ngps;  // every applied update is a fix or an IMU event
-        row[kScoreGpsN] = double(sc.ngps);
-        row[kScoreGpsNis] = group_sum(pva ? sc.nis[0] : 0.0);
-        row[kScoreGpsLogdetS] = group_sum(pva ? log_mant(sc.ldm[0], sc.lde[0]) : 0.0);
-        row[kScoreImuN] = double(nimu);
-        row[kScoreImuNis] = group_sum(live ? sc.nis[1] : 0.0);
-        // an aw chain's S is 2 x 2: its inert third pivot, exactly 2 every update, out of the exponent
-        row[kScoreImuLogdetS] = group_sum(live ? log_mant(sc.ldm[1], sc.lde[1] - (pva ? 0 : nimu)) : 0.0);
-        row[kScorePosN] = double(sc.npos);
-        row[kScorePosSse] = group_sum(pva ? sc.sse : 0.0);
-        const auto rs = span_rsrc(a.scores, 0, uint32_t(a.B) * 8u, kScoreRows);
-#pragma unroll
-        for (int r = 0; r < kScoreRows; ++r) {
-            const bool count = r == kScoreGpsN || r == kScoreImuN || r == kScorePosN;
-            stv(rs, c == 0 ? (uint32_t(r) * uint32_t(a.B) + uint32_t(f)) * 8u : kDropOffset,
-                bad && !count ? nan : row[r]);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// Fixed-interval (Rauch-Tung-Striebel) smoother over a sweep's filtered record (kf_smooth_sweep):
-// the backward pass over ckpt_x / ckpt_P of a sweep with ckpt_every = 1, in the sweep's layout (8
-// lanes per filter, lane c on axis chain c, one wave per workgroup).  P is block-diagonal over the
-// chains and F acts within a chain, so the smoother gain is block-diagonal too: each lane smooths
-// its own 3 x 3 block and holds the smoothed (x, P) of event t + 1 in registers, 3 + 6 values.
-// Row T - 1 is the filtered row.  For t = T - 2 .. 0, with (x_f, P_f) the filtered row t:
-//   etype[t + 1] == NONE: the forward step changed nothing, row t is row t + 1 (no arithmetic);
-//   otherwise  x_p = F x_f, P_p = F P_f F^T + Q dt[t + 1]   (ChainLane::predict, so P_p is the
-//                                                           forward run's own P_pred bit for bit)
-//              C = (P_f F^T) P_p^-1                         (in-lane LDL^T of P_p; its three pivots'
-//                                                           reciprocals are IEEE divisions, see there)
-//              x_s[t] = x_f + C (x_s[t + 1] - x_p)
-//              P_s[t] = P_f + C (P_s[t + 1] - P_p) C^T      (once per packed entry i <= j)
-// whatever the event at t + 1 was: its update is already in x_s[t + 1].  A lane without a chain
-// runs the same code on the unit block; an aw lane's inert third state stays (0, 1).
-// The inputs come backwards through ring_run (step s is t = T - 2 - s): etype and dt of t + 1 by
-// byte-range descriptors, the lane's 3 + 6 values of row t by a span descriptor with a 64-bit base
-// per event.  A row is loaded kSmoothDepth - 1 steps before the step that may overwrite it, so
-// sm_x == filt_x and sm_P == filt_P are legal.  No atomics, no LDS, no workspace.
-// A non-positive pivot of P_p or a NaN in a loaded row poisons the filter's group from that t down
-// to 0 (NaN rows, KF_ENOTSPD in sm_status); the rows above it are already stored.
-// ------------------------------------------------------------------------------------
-#ifndef KF_SMOOTH_DEPTH
-#define KF_SMOOTH_DEPTH KF_SWEEP_DEPTH
-#endif
-constexpr int kSmoothDepth = KF_SMOOTH_DEPTH;  // input ring of ref_smooth_kernel
-
-// One backward step's inputs for one lane: the event after the row, and the lane's part of the row
-template <typename T>
-struct SmoothIn {
-    int type;
-    double dt;
-    T x[3], P[6];
-};
-
-template <bool PARAMS>
-__device__ __forceinline__ auto smooth_consts(const SmoothArgs& a, int64_t f) {
-    if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
-    else return a.kc;
-}
-
-template <typename T, class M, bool CUSTOM, bool PARAMS = false>
-__global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArgs a) {
-    static_assert(!PARAMS || !CUSTOM, "per-filter constants in place of the handle's");
-    const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
-    const int64_t f = g / kGroup;
-    if (f >= a.B) return;  // whole groups leave together
-    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), smooth_consts<PARAMS>(a, f));
-    const int c = L.c;
-    const bool live = L.live;
-    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
-    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
-    uint32_t vx[3], vp[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vx[k] = L.xi[k] >= 0 ? uint32_t(L.xi[k]) * rb + off : kDropOffset;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vp[k] = L.pr[k] >= 0 ? uint32_t(L.pr[k]) * rb + off : kDropOffset;
-    const uint32_t v_tr = (L.xi[0] >= 0 && L.xi[0] < M::NTRAJ) ? uint32_t(L.xi[0]) * rb + off : kDropOffset;
-    const uint32_t v_ld = c == 0 ? off : kDropOffset;
-    const bool need_x = a.sm_x != nullptr, need_P = a.sm_P != nullptr;
-    const bool need_tr = a.sm_traj != nullptr, need_ld = a.sm_logdet != nullptr;
-
-    const int T_ = a.T;
-    const uint32_t S = uint32_t(T_);
-    const auto r_et = bytes_rsrc(a.etype, S), r_dt = bytes_rsrc(a.dt, S * 8u);
-    // row t of the filtered record: the lane's states and block rows (the rows it does not hold
-    // are dropped loads, 0, and the identity's entries)
-    auto load_row = [&](int t, T (&x)[3], T (&P)[6]) {
-        const auto rx = span_rsrc(a.filt_x, int64_t(t) * M::N, rb, M::N);
-        const auto rp = span_rsrc(a.filt_P, int64_t(t) * M::NBLK, rb, M::NBLK);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[k] = ldv(rx, vx[k], T(0));
-#pragma unroll
-        for (int k = 0; k < 6; ++k) P[k] = L.pr[k] >= 0 ? ldv(rp, vp[k], T(0)) : L.unit(k);
-    };
-    auto is_nan_row = [&](const T (&x)[3], const T (&P)[6]) {
-        bool nan = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) nan = nan || x[k] != x[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) nan = nan || P[k] != P[k];
-        return nan;
-    };
-    int32_t st = 0;
-    T xs[1][3], Ps[6];  // the smoothed row t + 1
-    auto poison = [&]() {
-        st = kNotSpd;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xs[0][k] = quiet_nan<T>();
-#pragma unroll
-        for (int k = 0; k < 6; ++k) Ps[k] = quiet_nan<T>();
-    };
-    // absent outputs: skipped by wave-uniform branches
-    auto store_row = [&](int t) {
-        if (need_x) {
-            const auto rx = span_rsrc(a.sm_x, int64_t(t) * M::N, rb, M::N);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) stv(rx, vx[k], xs[0][k]);
-        }
-        if (need_P) {
-            const auto rp = span_rsrc(a.sm_P, int64_t(t) * M::NBLK, rb, M::NBLK);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) stv(rp, vp[k], Ps[k]);
-        }
-        if (need_tr) stv(span_rsrc(a.sm_traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr, xs[0][0]);
-        if (need_ld) {
-            const T ld = group_sum(live ? chain_log_det(Ps) : T(0));
-            stv(span_rsrc(a.sm_logdet, t, rb, 1), v_ld, ld);
-        }
-    };
-
-    // row T - 1: the filtered row itself
-    load_row(T_ - 1, xs[0], Ps);
-    __builtin_amdgcn_s_waitcnt(0);
-    if (group_any(live && is_nan_row(xs[0], Ps))) poison();
-    store_row(T_ - 1);
-
-    const int n = T_ - 1;  // backward steps; step s is row t = T - 2 - s (past the end: row 0 again)
-    auto load = [&](int s, SmoothIn<T>& in) {
-        const int t = T_ - 2 - (s < n ? s : n - 1);
-        in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, uint32_t(t + 1), 0, 0));
-        in.dt = ldv(r_dt, uint32_t(t + 1) * 8u, 0.0);
-        load_row(t, in.x, in.P);
-    };
-    auto step = [&](int s, const SmoothIn<T>& in) {
-        const int t = T_ - 2 - s;
-        const int type = wave_uniform(in.type);  // every lane loaded the same type and dt
-        bool bad = is_nan_row(in.x, in.P);
-        if (type != 255) {
-            const T dt = T(in.dt);
-            T xp[1][3] = {{in.x[0], in.x[1], in.x[2]}};
-            T Pp[6], FP[3][3];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) Pp[k] = in.P[k];
-            L.template predict<1>(dt, xp, Pp, FP);
-            // P_p = L D L^T (unit lower L).  The pivots' reciprocals are IEEE divisions, not the
-            // updates' rcp_nr<kRefNewton>: P_f - C P_p C^T cancels (between applied updates P_s is
-            // orders of magnitude below P_f) and a relative error e of a pivot's reciprocal is the
-            // same wrong P_p^-1 in all three rows of C, so it reaches P_s as e P_f.  Measured against
-            // the longdouble truth at T = 300, in units of the plain float64 NumPy smoother's own
-            // error, budget 8 (profiles/rts_smoother/reciprocal_forms.log): with rcp_nr<kRefNewton>
-            // (2^-46) log det P_s reached 8.4 at the first case that failed; with a step of
-            // iterative refinement of C on top, P_s 8.9 and log det 36 (the residual rounds at
-            // eps |C| |P_p|); with divisions at most 2.0 and 4.8.  Three divisions a step
-            const T d0 = Pp[0];
-            const T i0 = T(1) / d0;
-            const T l10 = Pp[1] * i0, l20 = Pp[2] * i0;
-            const T v0 = l10 * d0;
-            const T d1 = fmaT(-l10, v0, Pp[3]);
-            const T i1 = T(1) / d1;
-            const T l21 = fmaT(-l20, v0, Pp[4]) * i1;
-            const T d2 = fmaT(-l21, l21 * d1, fmaT(-l20, l20 * d0, Pp[5]));
-            const T i2 = T(1) / d2;
-            bad = bad || !(d0 > T(0) && d1 > T(0) && d2 > T(0));
-            // C = (P_f F^T) P_p^-1, row i: P_p c = row i of (F P_f)^T = column i of F P_f
-            T C[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const T w0 = FP[0][i];
-                const T w1 = fmaT(-l10, w0, FP[1][i]);
-                const T w2 = fmaT(-l21, w1, fmaT(-l20, w0, FP[2][i]));
-                const T c2 = w2 * i2;
-                const T c1 = fmaT(-l21, c2, w1 * i1);
-                const T c0 = fmaT(-l20, c2, fmaT(-l10, c1, w0 * i0));
-                C[i][0] = c0, C[i][1] = c1, C[i][2] = c2;
-            }
-            T dx[3], D[6];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) dx[k] = xs[0][k] - xp[0][k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) D[k] = Ps[k] - Pp[k];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                xs[0][i] = fmaT(C[i][2], dx[2], fmaT(C[i][1], dx[1], fmaT(C[i][0], dx[0], in.x[i])));
-            T CD[3][3];  // C D
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    CD[i][j] = fmaT(C[i][2], D[tri<3>(2, j)], fmaT(C[i][1], D[tri<3>(1, j)], C[i][0] * D[tri<3>(0, j)]));
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = i; j < 3; ++j)
-                    Ps[tri<3>(i, j)] =
-                        fmaT(CD[i][2], C[j][2], fmaT(CD[i][1], C[j][1], fmaT(CD[i][0], C[j][0], in.P[tri<3>(i, j)])));
-            if (!L.pva) {  // the inert state, as after the forward run's updates
-                xs[0][2] = T(0);
-                Ps[2] = Ps[4] = T(0);
-                Ps[5] = T(1);
-            }
-        }
-        if (group_any(live && bad) || st != 0) poison();
-        store_row(t);
-    };
-    ring_run<kSmoothDepth, T, SmoothIn<T>>(n, load, step);
-    if (a.sm_status) {
-        const auto rs = span_rsrc(a.sm_status, 0, uint32_t(a.B) * 4u, 1);
-        __builtin_amdgcn_raw_buffer_store_b32(uint32_t(st), rs, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// ONE gated filter (B = 1, the adaptive threshold, kf_workers.py:959-1058) whose gate blocks
-// most updates, on one wave: lane c + 8 j is chain c (the chain kernel's lane layout) of event
-// slot j.  Every event that applies an update runs as ChainLane::event, the same in every slot.
-// After an event that did not, the wave looks ahead over the next 8 events at
-// once: between two updates the filter only predicts, and with the model's additive F (F(a) F(b)
-// = F(a + b)) and diagonal Q(dt) a run of predicts has a closed form,
-//   P_m = F(tau_m) (P + S_m) F(tau_m)^T,  S_m = sum_{i <= m} F(-tau_i) Q(dt_i) F(-tau_i)^T,
-// tau the time since the last event run (prefix sums over the slots), x_m = F(tau_m) x.  Slot j
-// takes event t + j; the first slot whose event would open the gate (GateBand on its closed-form
-// P_pred, a ballot over the slots) ends the run: the slots before it write their records at
-// once and hand their state on, and that event runs next as a chain-kernel event.  The closed
-// form rounds differently from one predict after another (records within 1.8e-12 relative of the
-// chain kernel's over 70,000 events, every flag equal); a gate decision could only differ within
-// that distance of the threshold (in f32 it does: f64 only).  KF_OPT_EVENTS_KERNEL = 4 runs it,
-// and kf_run_events' gated one-filter route when the chunked run falls back after updating at
-// most 1 event in 8 (launch_stream_choose).
-// ------------------------------------------------------------------------------------
-template <typename T, class M, bool CUSTOM>
-__global__ __launch_bounds__(64) void ref_chain_gated_kernel(const RefArgs a) {
-    if (a.skip && *a.skip) return;
-    const int lane = int(threadIdx.x);
-    const int slot = lane / kGroup;  // event slot of the look-ahead
-    const ChainLane<T, M, CUSTOM> L(lane & (kGroup - 1), a.kc);
-    const int c = L.c, ia = L.ia, ib = L.ib;
-    const bool pva = L.pva, live = L.live;
-    const auto& xi = L.xi;
-    const auto& pr = L.pr;
-    const auto& q = L.q;
-    const T* hx = static_cast<const T*>(a.x);
-    const T* hP = static_cast<const T*>(a.P);
-    T x[1][3], P[6];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) x[0][k] = xi[k] >= 0 ? hx[xi[k]] : T(0);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) P[k] = pr[k] >= 0 ? hP[pr[k]] : L.unit(k);
-    int32_t st = a.status[0];
-    GateBand<T> gate;
-    gate.init(a.threshold);
-    const T thr = T(a.threshold);
-    const T* pay = static_cast<const T*>(a.payload);
-    const bool cov = a.cov != nullptr, ldo = a.logdet != nullptr;
-    const int T_ = a.T;
-    // an event step's records (t wave-uniform): slot 0's lanes write, through buffer stores whose
-    // offsets drop the other slots' and the absent rows' stores (the chain kernel's form)
-    constexpr uint32_t rb = uint32_t(sizeof(T));
-    const uint32_t v_tr0 = slot == 0 && xi[0] >= 0 && xi[0] < M::NTRAJ ? uint32_t(xi[0]) * rb : kDropOffset;
-    uint32_t vp0[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vp0[k] = slot == 0 && pr[k] >= 0 ? uint32_t(pr[k]) * rb : kDropOffset;
-    const uint32_t v_ld0 = slot == 0 && c == 0 ? 0u : kDropOffset;
-    auto record_step = [&](int t, bool applied) {
-        stv(span_rsrc(a.traj, int64_t(t) * M::NTRAJ, rb, M::NTRAJ), v_tr0, x[0][0]);
-        if (cov) {
-            const auto rc = span_rsrc(a.cov, int64_t(t) * M::NBLK, rb, M::NBLK);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) stv(rc, vp0[k], P[k]);
-        }
-        if (ldo) {
-            const T ld = group_sum(live ? chain_log_det(P) : T(0));
-            st = (ld == ld) ? st : kNotSpd;
-            stv(span_rsrc(a.logdet, t, rb, 1), v_ld0, ld);
-        }
-        if (slot == 0 && c == 0 && a.updated) a.updated[t] = applied ? 1 : 0;
-    };
-    // a look-ahead run's records (events t0 + slot for the slots < n; t0 wave-uniform): one
-    // descriptor over the run's rows, each slot's lanes at their row, the other stores dropped
-    const uint32_t v_trr = xi[0] >= 0 && xi[0] < M::NTRAJ ? uint32_t(slot * M::NTRAJ + xi[0]) * rb : kDropOffset;
-    uint32_t vpr[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vpr[k] = pr[k] >= 0 ? uint32_t(slot * M::NBLK + pr[k]) * rb : kDropOffset;
-    const uint32_t v_ldr = c == 0 ? uint32_t(slot) * rb : kDropOffset;
-    auto record_run = [&](int t0, int n, const T (&xr)[3], const T (&Pr)[6]) {
-        const uint32_t wm = slot < n ? 0u : kDropOffset;
-        const uint32_t rows = uint32_t(T_ - t0 < 8 ? T_ - t0 : 8);
-        stv(span_rsrc(a.traj, int64_t(t0) * M::NTRAJ, rb, rows * M::NTRAJ), v_trr | wm, xr[0]);
-        if (cov) {
-            const auto rc = span_rsrc(a.cov, int64_t(t0) * M::NBLK, rb, rows * M::NBLK);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) stv(rc, vpr[k] | wm, Pr[k]);
-        }
-        if (ldo) {
-            const T ld = group_sum(live ? chain_log_det(Pr) : T(0));
-            st = (ld == ld || slot >= n) ? st : kNotSpd;
-            stv(span_rsrc(a.logdet, t0, rb, rows), v_ldr | wm, ld);
-        }
-        if (slot < n && c == 0 && a.updated) a.updated[t0 + slot] = 0;
-    };
-    int t = 0;
-    // a look-ahead after an event that did not update, unless the last one found its run over at
-    // once (then only after `cool` more such events: a regime of frequent updates stays on the
-    // chain kernel's event step)
-    int cool = 0, backoff = 0;
-    // event t's inputs, loaded one event ahead (t + 1 while t runs; a look-ahead that moves t
-    // reloads)
-    int nt = 0;
-    int ntype = T_ > 0 ? int(a.etype[0]) : 255;
-    double ndt = T_ > 0 ? a.dt[0] : 0.0;
-    T nva = T_ > 0 ? pay[ia] : T(0), nvb = T_ > 0 ? pay[ib] : T(0);
-    while (t < T_) {  // wave-uniform
-        // ---- event t, every slot the same arithmetic ----
-        if (nt != t) {
-            ntype = int(a.etype[t]);
-            ndt = a.dt[t];
-            nva = pay[int64_t(t) * 9 + ia];
-            nvb = pay[int64_t(t) * 9 + ib];
-        }
-        const int type = ntype;
-        const T dt = T(ndt);
-        const T va = nva, vb = nvb;
-        nt = t + 1;
-        if (nt < T_) {
-            ntype = int(a.etype[nt]);
-            ndt = a.dt[nt];
-            nva = pay[int64_t(nt) * 9 + ia];
-            nvb = pay[int64_t(nt) * 9 + ib];
-        }
-        const bool applied = L.event(type, dt, va, vb, true, gate, thr, x, P, st);
-        record_step(t, applied);
-        ++t;
-        // every lane holds the same decision (the gate's group ops, every slot the same event), but
-        // the compiler cannot know it: taken from lane 0, so that t and the loop stay scalar (a
-        // per-lane `continue` made t divergent, and with it every event's type branches)
-        if (__builtin_amdgcn_readfirstlane(int(applied)) || t >= T_) continue;
-        if (cool > 0) {
-            --cool;
-            continue;
-        }
-        for (;;) {  // look-aheads until a run ends (or the stream does)
-        // ---- look-ahead: slot j predicts to event t + j in closed form ----
-        const int e = t + slot;
-        const bool valid = e < T_;
-        const int ty = valid ? int(a.etype[e]) : 255;
-        const bool pred = valid && ty != 255;
-        const T dte = pred ? T(a.dt[e]) : T(0);
-        // tau: time since event t - 1 up to and including slot j's event (prefix over slots)
-        T tau = dte;
-#pragma unroll
-        for (int o = 1; o < 8; o *= 2) {
-            const T u = __shfl_up(tau, o * kGroup, 64);
-            tau += slot >= o ? u : T(0);
-        }
-        // this slot's term F(-tau) Q(dt) F(-tau)^T (G = F(-tau): rows (1, -tau, h'), (0, 1, g'), (0, 0, 1))
-        const T hm = pva ? T(0.5) * tau * tau : T(0), gm = pva ? -tau : T(0);
-        const T d0 = q[0] * dte, d1 = q[1] * dte, d2 = q[2] * dte;
-        T Sx[6];
-        Sx[0] = fmaT(hm * hm, d2, fmaT(tau * tau, d1, d0));
-        Sx[1] = fmaT(hm * gm, d2, -tau * d1);
-        Sx[2] = hm * d2;
-        Sx[3] = fmaT(gm * gm, d2, d1);
-        Sx[4] = gm * d2;
-        Sx[5] = d2;
-#pragma unroll
-        for (int o = 1; o < 8; o *= 2)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const T u = __shfl_up(Sx[k], o * kGroup, 64);
-                Sx[k] += slot >= o ? u : T(0);
-            }
-        // P_pred = F(tau) (P + S) F(tau)^T, F = [[1, tau, h], [0, 1, g], [0, 0, 1]]
-        const T h = pva ? T(0.5) * tau * tau : T(0), g = pva ? tau : T(0);
-        T A[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) A[k] = P[k] + Sx[k];
-        T B[3][3];  // F A
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            B[0][j] = fmaT(h, A[tri<3>(2, j)], fmaT(tau, A[tri<3>(1, j)], A[tri<3>(0, j)]));
-            B[1][j] = fmaT(g, A[tri<3>(2, j)], A[tri<3>(1, j)]);
-            B[2][j] = A[tri<3>(2, j)];
-        }
-        T Pp[6];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                T s = B[i][j];
-                if (j == 0) s = fmaT(B[i][2], h, fmaT(B[i][1], tau, s));
-                if (j == 1) s = fmaT(B[i][2], g, s);
-                Pp[tri<3>(i, j)] = s;
-            }
-        if (!pva) Pp[5] = P[5];  // the inert state of an aw lane
-        T xp[3] = {fmaT(h, x[0][2], fmaT(tau, x[0][1], x[0][0])), fmaT(g, x[0][2], x[0][1]), x[0][2]};
-        const bool opens = valid && (ty == kGps || ty == kImu) && gate.open(Pp, live, thr);
-        const uint64_t om = __builtin_amdgcn_ballot_w64(opens && c == 0);
-        const int nvalid = T_ - t < 8 ? T_ - t : 8;
-        const int n = om ? int(__builtin_ctzll(om)) / kGroup : nvalid;  // events of the predict run
-        record_run(t, n, xp, Pp);
-        st = __builtin_amdgcn_ballot_w64(st == kNotSpd) ? kNotSpd : st;  // a failed record in any slot
-        if (n > 0) {
-            const int src = (n - 1) * kGroup + c;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[0][k] = __shfl(xp[k], src, 64);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) P[k] = __shfl(Pp[k], src, 64);
-            t += n;
-        }
-        if (n < 4 && om) {  // a short run: look-aheads do not pay here, back off
-            backoff = backoff ? (backoff < 32 ? 2 * backoff : 32) : 1;
-            cool = backoff;
-        } else if (n >= 4) {
-            backoff = 0;
-        }
-        if (om || n < 8 || t >= T_) break;  // the run ended (its opening event runs next) or the stream did
-        }
-    }
-    if (slot == 0) {
-        T* ox = static_cast<T*>(a.x);
-        T* oP = static_cast<T*>(a.P);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (xi[k] >= 0) ox[xi[k]] = x[0][k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if (pr[k] >= 0) oP[pr[k]] = P[k];
-        if (c == 0) a.status[0] = st;
-    }
-}
-
-// ------------------------------------------------------------------------------------
 // Time-parallel run of ONE filter over a long event stream (kf_run_stream; the reference's own
 // use of run_kalman_filter_full, kf_workers.py:623-728, is one filter over a whole drive log).
 // The stream is cut into C chunks of L events that run as filters of the chain kernel:
@@ -2016,6 +216,12 @@ __global__ __launch_bounds__(64) void ref_chain_gated_kernel(const RefArgs a) {
 //    state; otherwise the sequential chain kernel, launched after these with skip = &check.ok,
 //    runs the stream as one filter and rewrites every record.
 // ------------------------------------------------------------------------------------
+#ifndef KF_STREAM_RECORD_PAIRS
+#define KF_STREAM_RECORD_PAIRS 1
+#endif
+// the records from the map pass two entries per thread (stream_records2_kernel; 0: one each)
+constexpr bool kStreamRecordPairs = KF_STREAM_RECORD_PAIRS != 0;
+
 template <class M>
 __device__ __forceinline__ int chain_state(int a, int q) {  // chain a (pva chains first), component q; -1: none
     return a < M::NP ? M::pva(a, q) : (q < 2 ? M::aw(a - M::NP, q) : -1);
@@ -4435,7 +2641,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KF_SCHED
     a.status[f] = L.st;
 }
 
-
 // ------------------------------------------------------------------------------------
 // Two-pass scheduled filter.  The greedy pick (kf_workers.py:195-213) compares two posterior
 // traces tr(P) - |P e_0|^2 / (P_00 + R) whose only difference is R: R_gps[0] for a fix, R_imu[0]
@@ -5029,42 +3234,6 @@ __global__ __launch_bounds__(kBlock) void schedule_finish_kernel(const uint64_t*
 }
 }  // namespace
 
-// kernel<..., CUSTOM> for a launch: the reference's constants (kc == nullptr) or the handle's
-#define KF_CUSTOM_DISPATCH(kc, ...)         \
-    do {                                    \
-        if (kc) {                           \
-            constexpr bool CUSTOM = true;   \
-            __VA_ARGS__;                    \
-        } else {                            \
-            constexpr bool CUSTOM = false;  \
-            __VA_ARGS__;                    \
-        }                                   \
-    } while (0)
-
-// the statement with M = M15 / M8 and T = double / float in scope (model is 15 or 8: the
-// launchers check); KF_REF_DISPATCH adds CUSTOM
-#define KF_DTYPE_DISPATCH(f64, ...) \
-    do {                            \
-        if (f64) {                  \
-            using T = double;       \
-            __VA_ARGS__;            \
-        } else {                    \
-            using T = float;        \
-            __VA_ARGS__;            \
-        }                           \
-    } while (0)
-#define KF_MODEL_DISPATCH(model, f64, ...)          \
-    do {                                            \
-        if ((model) == 15) {                        \
-            using M = M15;                          \
-            KF_DTYPE_DISPATCH(f64, __VA_ARGS__);    \
-        } else {                                    \
-            using M = M8;                           \
-            KF_DTYPE_DISPATCH(f64, __VA_ARGS__);    \
-        }                                           \
-    } while (0)
-#define KF_REF_DISPATCH(model, f64, kc, ...) KF_CUSTOM_DISPATCH(kc, KF_MODEL_DISPATCH(model, f64, __VA_ARGS__))
-
 hipError_t launch_ref15_random_picks(const Ref15SchedArgs& a, int32_t* pick, hipStream_t stream) {
     if (a.B <= 0 || a.T < 0 || !a.words || !a.words_used || !a.n_sel || !a.sel_time || !pick) return hipErrorInvalidValue;
     ref15_random_picks_kernel<<<dim3(unsigned((a.B + kBlock - 1) / kBlock)), kBlock, 0, stream>>>(a, pick);
@@ -5073,10 +3242,7 @@ hipError_t launch_ref15_random_picks(const Ref15SchedArgs& a, int32_t* pick, hip
 
 hipError_t launch_ref15_score(bool f64, const Ref15ScoreArgs& a, hipStream_t stream) {
     const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (f64) ref15_score_kernel<double, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        else ref15_score_kernel<float, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, ref15_score_kernel<T, CUSTOM><<<grid, kBlock, 0, stream>>>(a)));
     return hipGetLastError();
 }
 
@@ -5110,15 +3276,8 @@ hipError_t launch_ref15_scheduled(bool f64, const Ref15SchedArgs& a, hipStream_t
                 if (e != hipSuccess) return e;
                 c.order = a.order;
             }
-            KF_CUSTOM_DISPATCH(c.kc, {
-                if (c.pay_rec) {
-                    if (f64) ref15_apply_kernel<double, CUSTOM, 4, true, true><<<g4, 256, 0, stream>>>(c);
-                    else ref15_apply_kernel<float, CUSTOM, 4, true, true><<<g4, 256, 0, stream>>>(c);
-                } else {
-                    if (f64) ref15_apply_kernel<double, CUSTOM, 4, true><<<g4, 256, 0, stream>>>(c);
-                    else ref15_apply_kernel<float, CUSTOM, 4, true><<<g4, 256, 0, stream>>>(c);
-                }
-            });
+            KF_CUSTOM_DISPATCH(c.kc, KF_BOOL_DISPATCH(c.pay_rec, REC, KF_DTYPE_DISPATCH(f64,
+                ref15_apply_kernel<T, CUSTOM, 4, true, REC><<<g4, 256, 0, stream>>>(c))));
         } else {
             if (rnd) ref15_pick_kernel<4, true><<<g4, 256, 0, stream>>>(a);
             else if (a.group_waves == 4) ref15_pick_kernel<4><<<g4, 256, 0, stream>>>(a);
@@ -5131,137 +3290,57 @@ hipError_t launch_ref15_scheduled(bool f64, const Ref15SchedArgs& a, hipStream_t
                                                          a.order, static_cast<int>(a.B / 64), bits, stream);
                 if (e != hipSuccess) return e;
             }
-            KF_CUSTOM_DISPATCH(a.kc, {
+            KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, {
                 if (a.pay_rec) {  // payload records (kf_run_scheduled_rec): four-wave groups
-                    if (f64 && a.rec_time) ref15_apply_kernel<double, CUSTOM, 4, false, true, true><<<g4, 256, 0, stream>>>(a);
-                    else if (f64) ref15_apply_kernel<double, CUSTOM, 4, false, true><<<g4, 256, 0, stream>>>(a);
-                    else ref15_apply_kernel<float, CUSTOM, 4, false, true><<<g4, 256, 0, stream>>>(a);
+                    // RT (a.rec_time) is instantiated in fp64 only
+                    KF_BOOL_DISPATCH(f64 && a.rec_time, RT, if constexpr (!RT || sizeof(T) == 8)
+                        ref15_apply_kernel<T, CUSTOM, 4, false, true, RT><<<g4, 256, 0, stream>>>(a));
                 } else
 #if KF_APPLY_IMAGES == 2
                 if (a.group_waves == 4) {  // two images: 8 waves per CU in LDS
                     const dim3 g2(static_cast<unsigned>((a.B + 127) / 128));
-                    if (f64) ref15_apply_kernel<double, CUSTOM, 2, false><<<g2, 128, 0, stream>>>(a);
-                    else ref15_apply_kernel<float, CUSTOM, 2, false><<<g2, 128, 0, stream>>>(a);
+                    ref15_apply_kernel<T, CUSTOM, 2, false><<<g2, 128, 0, stream>>>(a);
                 } else
 #endif
                 if (a.group_waves == 4) {
-                    if (f64) ref15_apply_kernel<double, CUSTOM, 4, false><<<g4, 256, 0, stream>>>(a);
-                    else ref15_apply_kernel<float, CUSTOM, 4, false><<<g4, 256, 0, stream>>>(a);
+                    ref15_apply_kernel<T, CUSTOM, 4, false><<<g4, 256, 0, stream>>>(a);
                 } else {
-                    if (f64) ref15_apply_kernel<double, CUSTOM, 1, false><<<g1, 64, 0, stream>>>(a);
-                    else ref15_apply_kernel<float, CUSTOM, 1, false><<<g1, 64, 0, stream>>>(a);
+                    ref15_apply_kernel<T, CUSTOM, 1, false><<<g1, 64, 0, stream>>>(a);
                 }
-            });
+            }));
         }
         if (rnd) return hipGetLastError();  // random picks are never checked, so none is flagged
         Ref15SchedArgs b = a;  // the flagged filters (usually none: every lane leaves at once)
         b.only = a.flags;
-        KF_CUSTOM_DISPATCH(a.kc, {
-            if (f64) ref15_sched_kernel<double, CUSTOM><<<grid, kBlock, 0, stream>>>(b);
-            else ref15_sched_kernel<float, CUSTOM><<<grid, kBlock, 0, stream>>>(b);
-        });
+        KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, ref15_sched_kernel<T, CUSTOM><<<grid, kBlock, 0, stream>>>(b)));
         return hipGetLastError();
     }
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (lds) {
-            if (f64) ref15_sched_lds_kernel<double, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-            else ref15_sched_lds_kernel<float, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        } else {
-            if (f64) ref15_sched_kernel<double, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-            else ref15_sched_kernel<float, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        }
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, {
+        if (lds) ref15_sched_lds_kernel<T, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
+        else ref15_sched_kernel<T, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
+    }));
     return hipGetLastError();
 }
 
 namespace {
-template <typename T, class M, bool CUSTOM>
+// kf_run_events' one-lane-per-filter kernels; GATES (a.thresholds, kf_run_events_gates): the same
+// kernels with per-filter gates
+template <typename T, class M, bool CUSTOM, bool GATES>
 void ref_events_t(const RefArgs& a, hipStream_t stream, int variant) {
-    if (a.thresholds) {  // kf_run_events_gates: the same three kernels with per-filter gates
-        if (variant == kEventsLds) {
-            const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-            if (a.cov) ref_events_lds_kernel<T, M, true, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-            else ref_events_lds_kernel<T, M, false, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-        } else if (variant == kEventsChain) {
-            const dim3 cgrid(static_cast<unsigned>((a.B * kGroup + kBlock - 1) / kBlock));
-            ref_chain_kernel<T, M, false, CUSTOM, 1, true><<<cgrid, kBlock, 0, stream>>>(a);
-        } else {
-            const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-            ref_events_kernel<T, M, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-        }
-        return;
-    }
-    if (variant == kEventsLds) {
-        const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-        if (a.cov) ref_events_lds_kernel<T, M, true, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        else ref_events_lds_kernel<T, M, false, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-    } else if (variant == kEventsChain) {
-        const dim3 cgrid(static_cast<unsigned>((a.B * kGroup + kBlock - 1) / kBlock));
-        ref_chain_kernel<T, M, false, CUSTOM><<<cgrid, kBlock, 0, stream>>>(a);
-    } else if (variant == kEventsGated) {
-        ref_chain_gated_kernel<T, M, CUSTOM><<<1, 64, 0, stream>>>(a);
-    } else {
-        const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-        ref_events_kernel<T, M, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-    }
-}
-template <typename T, class M, bool CUSTOM>
-void ref_stream_t(const RefArgs& a, hipStream_t stream, int nv) {
-    if (nv == 4) {
-        const dim3 vgrid(static_cast<unsigned>((a.B * chain_lanes<4>() + kBlock - 1) / kBlock));
-        ref_chain_kernel<T, M, true, CUSTOM, 4><<<vgrid, kBlock, 0, stream>>>(a);
-    } else {
-        const dim3 cgrid(static_cast<unsigned>((a.B * kGroup + kBlock - 1) / kBlock));
-        ref_chain_kernel<T, M, true, CUSTOM><<<cgrid, kBlock, 0, stream>>>(a);
-    }
+    const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+    if (variant == kEventsLds)
+        KF_BOOL_DISPATCH(a.cov, COV, ref_events_lds_kernel<T, M, COV, CUSTOM, GATES><<<grid, kBlock, 0, stream>>>(a));
+    else
+        ref_events_kernel<T, M, CUSTOM, GATES><<<grid, kBlock, 0, stream>>>(a);
 }
 }  // namespace
 
 hipError_t launch_ref_events(int model, bool f64, const RefArgs& a, hipStream_t stream, int variant) {
     if (model != 15 && model != 8) return hipErrorInvalidValue;
     if (a.thresholds && (variant == kEventsGated || a.s_len != 0)) return hipErrorInvalidValue;
-    KF_REF_DISPATCH(model, f64, a.kc, ref_events_t<T, M, CUSTOM>(a, stream, variant));
-    return hipGetLastError();
-}
-
-hipError_t launch_ref_stream(int model, bool f64, const RefArgs& a, hipStream_t stream, int nv) {
-    if (a.s_len <= 0 || a.s_nchunks <= 0 || (nv != 1 && nv != 4)) return hipErrorInvalidValue;
-    if (model != 15 && model != 8) return hipErrorInvalidValue;
-    KF_REF_DISPATCH(model, f64, a.kc, ref_stream_t<T, M, CUSTOM>(a, stream, nv));
-    return hipGetLastError();
-}
-
-hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream) {
-    if (a.B <= 0 || a.T < 0 || !a.tails || (model != 15 && model != 8)) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM, true><<<grid, kSweepBlock, 0, stream>>>(a));
-    return hipGetLastError();
-}
-
-hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t stream, bool scored) {
-    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || (!a.thresholds && !a.consts)) return hipErrorInvalidValue;
-    if (scored && (!a.consts || !a.scores)) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    if (a.consts && scored)
-        KF_MODEL_DISPATCH(model, f64,
-                          ref_sweep_kernel<T, M, false, false, true, true><<<grid, kSweepBlock, 0, stream>>>(a));
-    else if (a.consts)
-        KF_MODEL_DISPATCH(model, f64, ref_sweep_kernel<T, M, false, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
-    else
-        KF_REF_DISPATCH(model, f64, a.kc, ref_sweep_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
-    return hipGetLastError();
-}
-
-hipError_t launch_ref_smooth(int model, const SmoothArgs& a, hipStream_t stream) {
-    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || !a.filt_x || !a.filt_P || !a.etype || !a.dt)
-        return hipErrorInvalidValue;
-    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
-    if (a.consts)
-        KF_MODEL_DISPATCH(model, true, if constexpr (sizeof(T) == 8)
-                                           ref_smooth_kernel<T, M, false, true><<<grid, kSweepBlock, 0, stream>>>(a));
-    else
-        KF_REF_DISPATCH(model, true, a.kc, if constexpr (sizeof(T) == 8)
-                                               ref_smooth_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
+    if (variant == kEventsChain || variant == kEventsGated) return launch_ref_events_chain(model, f64, a, stream, variant);
+    KF_REF_DISPATCH(model, f64, a.kc,
+                    KF_BOOL_DISPATCH(a.thresholds, GATES, ref_events_t<T, M, CUSTOM, GATES>(a, stream, variant)));
     return hipGetLastError();
 }
 
@@ -5287,8 +3366,7 @@ void stream_phase(int phase, const StreamArgs& a, hipStream_t stream) {
         }
         case kStreamPhaseLftMaps: {
             const int64_t lanes = a.C * a.np * lft_map_chains<M>(a.sym != 0) * kLftStride;
-            if (a.kc) stream_lft_maps_kernel<T, M, true><<<grid(lanes), kBlock, 0, stream>>>(a);
-            else stream_lft_maps_kernel<T, M, false><<<grid(lanes), kBlock, 0, stream>>>(a);
+            KF_CUSTOM_DISPATCH(a.kc, stream_lft_maps_kernel<T, M, CUSTOM><<<grid(lanes), kBlock, 0, stream>>>(a));
             break;
         }
         case kStreamPhaseLftStart: {
@@ -5377,13 +3455,9 @@ hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t s
 hipError_t launch_ref15_combos(bool f64, const Ref15ComboArgs& a, hipStream_t stream) {
     if (a.n_events > kMaxEvents) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (f64) ref15_combo_kernel<double, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-        else ref15_combo_kernel<float, CUSTOM><<<grid, kBlock, 0, stream>>>(a);
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, ref15_combo_kernel<T, CUSTOM><<<grid, kBlock, 0, stream>>>(a)));
     return hipGetLastError();
 }
-
 
 void set_search_band(Ref15SearchArgs& a, bool f64) {
     // the threshold as the kernels compare it (T(threshold)); (mantissa, exponent) pairs whose
@@ -5422,15 +3496,8 @@ hipError_t launch_ref15_search_end(bool f64, const Ref15SearchArgs& a, hipStream
         return hipErrorInvalidValue;
     // the extensions' table (group i: extension gblk[i], first wave gitem[i], then the total)
     const dim3 grid(unsigned(a.gitem[a.n_groups]));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (a.sym) {
-            if (f64) ref15_search_end_kernel<double, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-            else ref15_search_end_kernel<float, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-        } else {
-            if (f64) ref15_search_end_kernel<double, CUSTOM, false><<<grid, 64, 0, stream>>>(a);
-            else ref15_search_end_kernel<float, CUSTOM, false><<<grid, 64, 0, stream>>>(a);
-        }
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_BOOL_DISPATCH(a.sym, SYM, KF_DTYPE_DISPATCH(f64,
+        ref15_search_end_kernel<T, CUSTOM, SYM><<<grid, 64, 0, stream>>>(a))));
     return hipGetLastError();
 }
 
@@ -5442,15 +3509,8 @@ hipError_t launch_ref15_search_windows(bool f64, bool sym, const Ref15WindowArgs
         return hipErrorInvalidValue;
     const dim3 grid(unsigned((max_lanes + 63) / 64), unsigned(W));
     const size_t lds = search_binom_lds_bytes(n_max, k_max + 1);
-    KF_CUSTOM_DISPATCH(kc, {
-        if (sym) {
-            if (f64) ref15_search_windows_kernel<double, CUSTOM, true><<<grid, 64, lds, stream>>>(wins, binom, kc);
-            else ref15_search_windows_kernel<float, CUSTOM, true><<<grid, 64, lds, stream>>>(wins, binom, kc);
-        } else {
-            if (f64) ref15_search_windows_kernel<double, CUSTOM, false><<<grid, 64, lds, stream>>>(wins, binom, kc);
-            else ref15_search_windows_kernel<float, CUSTOM, false><<<grid, 64, lds, stream>>>(wins, binom, kc);
-        }
-    });
+    KF_CUSTOM_DISPATCH(kc, KF_BOOL_DISPATCH(sym, SYM, KF_DTYPE_DISPATCH(f64,
+        ref15_search_windows_kernel<T, CUSTOM, SYM><<<grid, 64, lds, stream>>>(wins, binom, kc))));
     return hipGetLastError();
 }
 
@@ -5467,15 +3527,8 @@ hipError_t launch_ref15_search_head(bool f64, const Ref15SearchArgs& a, hipStrea
         return hipErrorInvalidValue;
     const dim3 grid(unsigned((a.n_child + 63) / 64));
     const size_t lds = search_binom_lds_bytes(a.n_events, a.k + 1);
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (a.sym) {
-            if (f64) ref15_search_head_kernel<double, CUSTOM, true><<<grid, 64, lds, stream>>>(a);
-            else ref15_search_head_kernel<float, CUSTOM, true><<<grid, 64, lds, stream>>>(a);
-        } else {
-            if (f64) ref15_search_head_kernel<double, CUSTOM, false><<<grid, 64, lds, stream>>>(a);
-            else ref15_search_head_kernel<float, CUSTOM, false><<<grid, 64, lds, stream>>>(a);
-        }
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_BOOL_DISPATCH(a.sym, SYM, KF_DTYPE_DISPATCH(f64,
+        ref15_search_head_kernel<T, CUSTOM, SYM><<<grid, 64, lds, stream>>>(a))));
     return hipGetLastError();
 }
 
@@ -5519,38 +3572,16 @@ hipError_t launch_ref15_search(bool f64, const Ref15SearchArgs& a, bool child_ma
         Ref15SearchArgs b;
         uint64_t items = 0, waves = 0;
         if (!cm_items(a, b, items, waves)) return hipErrorInvalidValue;
-        KF_CUSTOM_DISPATCH(a.kc, {
-            if (a.sym) {
-                if (f64) ref15_search_cm_kernel<double, CUSTOM, true><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-                else ref15_search_cm_kernel<float, CUSTOM, true><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-            } else {
-                if (f64) ref15_search_cm_kernel<double, CUSTOM, false><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-                else ref15_search_cm_kernel<float, CUSTOM, false><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-            }
-        });
+        KF_CUSTOM_DISPATCH(a.kc, KF_BOOL_DISPATCH(a.sym, SYM, KF_DTYPE_DISPATCH(f64,
+            ref15_search_cm_kernel<T, CUSTOM, SYM><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items))));
         return hipGetLastError();
     }
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (!a.pm_regs) {
-            const dim3 grid(static_cast<unsigned>((a.n_par + 63) / 64));
-            if (a.sym) {
-                if (f64) ref15_search_pm_kernel<double, true, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-                else ref15_search_pm_kernel<float, true, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-            } else {
-                if (f64) ref15_search_pm_kernel<double, true, CUSTOM, false><<<grid, 64, 0, stream>>>(a);
-                else ref15_search_pm_kernel<float, true, CUSTOM, false><<<grid, 64, 0, stream>>>(a);
-            }
-        } else {
-            const dim3 grid(static_cast<unsigned>((a.n_par + kBlock - 1) / kBlock));
-            if (a.sym) {
-                if (f64) ref15_search_pm_kernel<double, false, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-                else ref15_search_pm_kernel<float, false, CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-            } else {
-                if (f64) ref15_search_pm_kernel<double, false, CUSTOM, false><<<grid, kBlock, 0, stream>>>(a);
-                else ref15_search_pm_kernel<float, false, CUSTOM, false><<<grid, kBlock, 0, stream>>>(a);
-            }
-        }
-    });
+    // PLDS: the parents' covariances in LDS, one wave per workgroup; otherwise (a.pm_regs) in registers
+    KF_CUSTOM_DISPATCH(a.kc, KF_BOOL_DISPATCH(!a.pm_regs, PLDS, KF_BOOL_DISPATCH(a.sym, SYM, KF_DTYPE_DISPATCH(f64, {
+        constexpr unsigned block = PLDS ? 64 : kBlock;
+        const dim3 grid(static_cast<unsigned>((a.n_par + block - 1) / block));
+        ref15_search_pm_kernel<T, PLDS, CUSTOM, SYM><<<grid, block, 0, stream>>>(a);
+    }))));
     return hipGetLastError();
 }
 
@@ -5563,17 +3594,12 @@ hipError_t launch_ref15_search_pair(bool f64, const Ref15SearchArgs& a, bool chi
         Ref15SearchArgs b;
         uint64_t items = 0, waves = 0;
         if (!cm_items(a, b, items, waves)) return hipErrorInvalidValue;
-        KF_CUSTOM_DISPATCH(a.kc, {
-            if (f64) ref15_search_cm_kernel<double, CUSTOM, true, true><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-            else ref15_search_cm_kernel<float, CUSTOM, true, true><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items);
-        });
+        KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64,
+            ref15_search_cm_kernel<T, CUSTOM, true, true><<<dim3(unsigned(waves)), 64, 0, stream>>>(b, items)));
         return hipGetLastError();
     }
     const dim3 grid(static_cast<unsigned>((a.n_par + 63) / 64));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (f64) ref15_search_pair_kernel<double, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-        else ref15_search_pair_kernel<float, CUSTOM, true><<<grid, 64, 0, stream>>>(a);
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_DTYPE_DISPATCH(f64, ref15_search_pair_kernel<T, CUSTOM, true><<<grid, 64, 0, stream>>>(a)));
     return hipGetLastError();
 }
 
@@ -5586,10 +3612,7 @@ hipError_t launch_ref15_schedule(const ScheduleArgs& a, bool leaf, hipStream_t s
         return hipErrorInvalidValue;
     if (!leaf && a.n_nodes > kScheduleMaxNodes) return hipErrorInvalidValue;
     const dim3 grid(schedule_grid(a.n_nodes));
-    KF_CUSTOM_DISPATCH(a.kc, {
-        if (leaf) ref15_schedule_kernel<CUSTOM, true><<<grid, kBlock, 0, stream>>>(a);
-        else ref15_schedule_kernel<CUSTOM, false><<<grid, kBlock, 0, stream>>>(a);
-    });
+    KF_CUSTOM_DISPATCH(a.kc, KF_BOOL_DISPATCH(leaf, LEAF, ref15_schedule_kernel<CUSTOM, LEAF><<<grid, kBlock, 0, stream>>>(a)));
     return hipGetLastError();
 }
 

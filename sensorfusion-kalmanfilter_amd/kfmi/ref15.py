@@ -44,7 +44,7 @@ def _block_rows(pva, aw):
     return rows
 
 
-# block-packed row r -> (i, j) of the dense covariance, per model (csrc/kf_ref.hip, include/kf.h)
+# block-packed row r -> (i, j) of the dense covariance, per model (csrc/kf_ref_model.h, include/kf.h)
 _LAYOUT = {
     # n: (rows, model name) — REF15 chains (pos, vel, acc)_i = (i, 6+i, 12+i), (att, rate)_i = (3+i, 9+i)
     15: (_block_rows([(0, 6, 12), (1, 7, 13), (2, 8, 14)], [(3, 9), (4, 10), (5, 11)]), 'ref15'),

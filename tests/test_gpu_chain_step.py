@@ -1,4 +1,4 @@
-"""The 8-lanes-per-filter kernels share one event step (ChainLane::event in csrc/kf_ref.hip): on
+"""The 8-lanes-per-filter kernels share one event step (ChainLane::event in csrc/kf_ref_chainlane.h): on
 the same short stream the chain kernel (scalar gate), the chain kernel with per-filter gates, the
 sweep, a tail over the whole stream and the look-ahead kernel give the same bits — needs an
 MI355X."""
