@@ -506,7 +506,7 @@ struct Ref15SchedArgs {
 
 enum class Op { Run, Predict, Update, Step, Reset };  // Step: predict + update (kf_capi's deferral)
 
-// Launchers (kf_cv.hip, kf_ref.hip, kf_ref_chain.hip).  Return hipSuccess or the launch error.
+// Launchers (kf_cv.hip, kf_ref.hip and the kf_ref_*.hip units).  Return hipSuccess or the launch error.
 hipError_t launch_cv(int axes, bool f64, Op op, const CvArgs& a, hipStream_t stream);
 // *flag |= 1 if any filter's P couples different axes (flag: device int, zeroed by the caller).
 hipError_t launch_cv_offblock(int axes, bool f64, const CvArgs& a, int* flag, hipStream_t stream);

@@ -1,13 +1,13 @@
 // What the 8-lanes-per-filter kernels share: the lane group's DPP exchanges, the banded gate, one
 // lane's chain with its event step (ChainLane) and the input ring.  Like kf_ref_model.h it declares
-// in an anonymous namespace: only kf_ref_chain.hip and kf_ref.hip (its stream phases) include it.
+// in an anonymous namespace: only kf_ref_chain.hip and kf_ref_sweep.hip include it.
 #pragma once
 #include "kf_ref_model.h"
 
 namespace kfmi {
 namespace {
 
-constexpr int kGroup = 8;  // lanes per filter: one per axis chain (kf_ref_chain.hip)
+constexpr int kGroup = 8;  // lanes per filter: one per axis chain
 
 // Sums / ORs over the 8-lane group with DPP (a VALU-latency lane exchange, no LDS round trip):
 // quad_perm [1,0,3,2] (xor 1), quad_perm [2,3,0,1] (xor 2), then row_half_mirror (lane i <-> 7-i

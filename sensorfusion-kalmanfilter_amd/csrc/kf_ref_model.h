@@ -17,9 +17,11 @@
 //   rows 6NP+3c .. 6NP+3c+2 : aw chain c upper triangle (tt tw ww), c = 0..NA-1
 // State x [N][B] in the reference's order.
 //
-// This header is the model layer of the units kf_ref.hip and kf_ref_chain.hip: the constants,
-// M15 / M8, the noise tables, Chains, FilterGate and the launchers' dispatch macros.  It declares
-// in an anonymous namespace, as the units' kernels do, so only those units include it.
+// This header is the model layer of the units kf_ref_lane.hip, kf_ref_search.hip and kf_ref.hip, and
+// through kf_ref_chainlane.h of kf_ref_chain.hip and kf_ref_sweep.hip: the constants, M15 / M8, the
+// noise tables, Chains, FilterGate, the few declarations that two families share and the launchers'
+// dispatch macros.  It declares in an anonymous namespace, as the units' kernels do, so only those
+// units include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -402,6 +404,18 @@ __device__ __forceinline__ FilterGate<T> gate_of(const double* thresholds, int64
     // -inf is "always update": the gate is not evaluated; +inf and NaN fail every comparison
     return FilterGate<T>{t != -__builtin_inf(), T(t)};
 }
+
+// What more than one family reads.
+// s_waitcnt immediates; read by the lane unit's LDS kernel and the scheduler's LDS kernels
+constexpr int vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
+constexpr int lgkmcnt0_imm = 15 | (7 << 4) | (0 << 8) | (3 << 14);  // LDS reads drained, vmcnt untouched
+
+// a search's candidate events at most; read by the combos and search kernels and their launchers
+constexpr int kMaxEvents = 64;
+
+// the 15-state lane; read by the combos, search and scheduler kernels
+template <typename T, bool CUSTOM = false>
+using Ref15 = Chains<T, M15, CUSTOM>;
 
 }  // namespace
 

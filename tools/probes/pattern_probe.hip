@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void pattern_burst_kernel(const void* u, const
     if (h) burst(T_ - h, h);
 }
 
-// ref_events_lds_kernel's memory instructions (kf_ref.hip): the state rows loaded once and
+// ref_events_lds_kernel's memory instructions (kf_ref_lane.hip): the state rows loaded once and
 // stored once, each event's payload / dt / type moved HBM -> LDS by buffer_load ... lds into
 // one of two per-wave images while the previous event is consumed, the same counted waits, and
 // per event the six trajectory rows, the log-det row and the (zero-length) updated row stored.
