@@ -1289,7 +1289,7 @@ int run_stream_impl(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
                                                align256(sizeof(double) * 4 * nch * C)
                                          : 0;
     const int64_t ntiles = (C + kfmi::kStreamScanTile - 1) / kfmi::kStreamScanTile;
-    // more tiles than one scan round: the top kernel writes the tile starts (kf_ref.hip phase 3)
+    // more tiles than one scan round: the top kernel writes the tile starts (kf_ref_stream.hip phase 3)
     const bool top = ntiles > kfmi::kStreamScanTile;
     const size_t top_bytes = top ? align256(sizeof(double) * 3 * nch * ntiles) : 0;
     const size_t need = 256 + 2 * bank1 + bank4 + 2 * align256(sizeof(double) * 12 * nch * C) +

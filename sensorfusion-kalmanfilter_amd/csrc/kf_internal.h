@@ -275,7 +275,7 @@ constexpr int kStreamBadFilter = 1, kStreamBadStart = 2;
 // records from the map pass: phase 8 = trajectories from the variants and the chunk starts
 constexpr int kStreamPhaseScanTiles = 2, kStreamPhaseTop = 3, kStreamPhaseStarts = 4, kStreamPhaseFinish = 5,
               kStreamPhaseRecords = 8;
-constexpr int64_t kStreamScanTile = 256;  // chunks per scan tile (kScanTile in kf_ref.hip)
+constexpr int64_t kStreamScanTile = 256;  // chunks per scan tile (kScanTile in kf_ref_stream.hip)
 
 // Brute-force search over k-subsets of n candidate events (kf_workers.py:22-97, 1218-1392):
 // lane f evaluates combination number combo_offset + f in itertools.combinations order.
@@ -506,7 +506,7 @@ struct Ref15SchedArgs {
 
 enum class Op { Run, Predict, Update, Step, Reset };  // Step: predict + update (kf_capi's deferral)
 
-// Launchers (kf_cv.hip, kf_ref.hip and the kf_ref_*.hip units).  Return hipSuccess or the launch error.
+// Launchers (kf_cv.hip and the kf_ref_*.hip units).  Return hipSuccess or the launch error.
 hipError_t launch_cv(int axes, bool f64, Op op, const CvArgs& a, hipStream_t stream);
 // *flag |= 1 if any filter's P couples different axes (flag: device int, zeroed by the caller).
 hipError_t launch_cv_offblock(int axes, bool f64, const CvArgs& a, int* flag, hipStream_t stream);
@@ -563,7 +563,7 @@ hipError_t launch_ref15_score(bool f64, const Ref15ScoreArgs& a, hipStream_t str
 hipError_t launch_ref15_scheduled(bool f64, const Ref15SchedArgs& a, hipStream_t stream);
 // random_schedule's picks only (a.words): pick [T][B] event indices, a.sel_time, a.n_sel, a.words_used
 hipError_t launch_ref15_random_picks(const Ref15SchedArgs& a, int32_t* pick, hipStream_t stream);
-// descending stable radix sort of n (key, value) pairs on the key's low `bits` bits (kf_ingest.hip,
+// descending stable radix sort of n (key, value) pairs on the key's low `bits` bits (kf_sort.hip,
 // hipCUB); tmp == nullptr: *tmp_bytes = the scratch it needs
 hipError_t sort_pairs_desc_u32(void* tmp, size_t* tmp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
                                const uint32_t* vals_in, uint32_t* vals_out, int n, int bits, hipStream_t stream);

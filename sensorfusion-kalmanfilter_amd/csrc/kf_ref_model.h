@@ -17,8 +17,9 @@
 //   rows 6NP+3c .. 6NP+3c+2 : aw chain c upper triangle (tt tw ww), c = 0..NA-1
 // State x [N][B] in the reference's order.
 //
-// This header is the model layer of the units kf_ref_lane.hip, kf_ref_search.hip and kf_ref.hip, and
-// through kf_ref_chainlane.h of kf_ref_chain.hip and kf_ref_sweep.hip: the constants, M15 / M8, the
+// This header is the model layer of the units kf_ref_lane.hip, kf_ref_search.hip, kf_ref_stream.hip,
+// kf_ref_scheduler.hip and kf_ref_schedule_search.hip, and through kf_ref_chainlane.h of
+// kf_ref_chain.hip and kf_ref_sweep.hip: the constants, M15 / M8, the
 // noise tables, Chains, FilterGate, the few declarations that two families share and the launchers'
 // dispatch macros.  It declares in an anonymous namespace, as the units' kernels do, so only those
 // units include it.

@@ -273,7 +273,7 @@ def test_many_chunks_multi_round_scan():
 
 def test_many_tiles_top_scan():
     """Far more chunks than one scan round of tiles (2.2M events in chunks of 8: 275,000 chunks,
-    1,075 tiles, five rounds of the top kernel, kf_ref.hip phase 3, instead of every starts block
+    1,075 tiles, five rounds of the top kernel, kf_ref_stream.hip phase 3, instead of every starts block
     redoing its prefix): records, final state and covariance equal the single filter's."""
     et, dt, pay, x0 = _stream(2_200_000, seed=31, skips=40)
     seq = _sequential(et, dt, pay, x0)

@@ -162,7 +162,7 @@ def test_class_args_worker_checks_formulas():
 
 
 def legacy_choice_emulation(words, lens):
-    """What kf_run_scheduled_random's legacy_choice does (kf_ref.hip), in Python: per window of
+    """What kf_run_scheduled_random's legacy_choice does (kf_ref_scheduler.hip), in Python: per window of
     n queued events, no output for n = 1, else outputs & (smallest 2^k - 1 >= n - 1) until one is
     <= n - 1.  Returns (draws, outputs taken)."""
     wp, out = 0, []
