@@ -302,6 +302,71 @@ int kf_run(kf_batch* handle, int T, double dt, const double* dt_steps, const voi
            const void* z, const uint8_t* mask, int update_every, void* traj, void* logdet,
            void* stream);
 
+/* kf_run that also records the filtered covariance: the forward half of a smoothed
+ * constant-velocity track (kf_smooth_run is the backward half).  KF_MODEL_CV2 / KF_MODEL_CV3, both
+ * dtypes.  Every argument it shares with kf_run means what it means there: optional dt_steps, u
+ * (NULL = zero control) and mask; a held-back kf_predict runs first; T = 0 is KF_OK; traj and
+ * logdet may be NULL.
+ * cov: device [T][3 d][B] in the handle's dtype, d = 2 | 3 axes, so 6 (KF_MODEL_CV2) or 9
+ * (KF_MODEL_CV3) rows per step: rows 3 i .. 3 i + 2 are axis i's (pp, pv, vv) = (P[i][i],
+ * P[i][d + i], P[d + i][d + i]) after step t, its update included.  May be NULL.
+ * The block-packed record can only hold a covariance that is block-diagonal over the axes.
+ * KF_EINVAL, before anything is queued (a held-back predict included):
+ *   the handle's P is not known to be block-diagonal (kf_alloc / kf_reset leave it so; kf_set_state
+ *   checks the P it is given on the device);
+ *   R has a non-zero off-diagonal entry (the update would couple the axes);
+ *   the handle is a reference model.
+ * Bit for bit: the handle's state and status, traj and logdet are those of the kf_run call with
+ * the same inputs and both of its records, on whichever of its kernels (KF_OPT_CV_KERNEL), and do
+ * not depend on which of traj, cov and logdet are NULL; cov[T - 1] holds the same-axis entries of
+ * kf_get_state's P.  (kf_run itself, in fp64 with a scalar dt, u and no mask, rounds Q dt + P once
+ * less when one of its records is NULL than when both are written; this call always matches the
+ * latter.)  Asynchronous on `stream`, capturable, allocates nothing.  The reference keeps no covariance history; its loop's P after each step
+ * (kf_workers.py:691, 711) is what a row holds. */
+int kf_run_rec(kf_batch* handle, int T, double dt, const double* dt_steps, const void* u,
+               const void* z, const uint8_t* mask, int update_every,
+               void* traj, void* cov, void* logdet, void* stream);
+
+/* Fixed-interval (Rauch-Tung-Striebel) smoother over a kf_run_rec record: what each of the B
+ * filters could know about every step with the whole interval in hand; kf_smooth_sweep's
+ * counterpart for the constant-velocity models, one filter per lane.  f64 KF_MODEL_CV2 /
+ * KF_MODEL_CV3 handles only (an f32 handle or a reference model: KF_EINVAL).
+ * filt_x [T][n][B] is kf_run_rec's traj and filt_P [T][3 d][B] its cov; any record in that layout
+ * is accepted.  dt / dt_steps / u are the forward run's (u NULL = zero control).  The handle gives
+ * the model, B, q_pos and q_vel only: its state, its status and a held-back predict are neither
+ * read nor touched.
+ *
+ * Row T - 1 of the result is the filtered row.  For t = T - 2 .. 0, per axis, with (x_f, P_f) =
+ * row t and d = dt[t + 1]:
+ *   x_p = F x_f + G u[t + 1],  P_p = F P_f F^T + Q d    (the forward step's own predict lines)
+ *   C = (P_f F^T) P_p^-1
+ *   x_s[t] = x_f + C (x_s[t + 1] - x_p)
+ *   P_s[t] = P_f + C (P_s[t + 1] - P_p) C^T
+ * whether step t + 1 ended with a fix or not: its update is already in x_s[t + 1].  The gain comes
+ * from a 2 x 2 LDL^T of P_p whose two pivots are divided by exactly (P_f - C P_p C^T cancels: P_f
+ * reaches thousands of times P_s between fixes); P_s is formed once per packed entry.
+ *
+ * Outputs, device, each may be NULL: sm_x [T][n][B], sm_P [T][3 d][B], sm_logdet [T][B] (log det
+ * P_s, from the pivots in kf_run's order and form), sm_status [B] int32 (written for every filter:
+ * 0 or KF_ENOTSPD).  sm_x == filt_x and / or sm_P == filt_P exactly is legal (every row is read
+ * before it is written); any other overlap is undefined and not checked.
+ * A NaN in a loaded row (state, covariance or control) or a non-positive pivot of P_p fails that
+ * filter alone: its rows from that t down to 0 are NaN and its sm_status is KF_ENOTSPD; its rows
+ * above, and its neighbours, are untouched.  T = 0 is KF_OK and writes nothing; T = 1 copies the
+ * filtered row.
+ *
+ * Bit for bit: row T - 1 is the filtered row, and a filter's rows do not depend on B, on its place
+ * in its wave, on which outputs are NULL or on running in place.  Memory: the record is 120 B
+ * (KF_MODEL_CV2: 80 B) per step and filter.  Asynchronous on `stream`, capturable; no workspace.
+ * Limits: every row is addressed from a 64-bit base, so T has no limit of its own and B only
+ * kf_alloc's (8 B < 2 GiB).  KF_EINVAL before anything is queued: T < 0, a negative or NaN scalar
+ * dt, NULL filt_x or filt_P with T > 0.  Not built: a non-block-diagonal P or non-diagonal R, f32,
+ * and a smoothed row for the state before step 0.  The reference has no smoother; this is the
+ * backward half of the textbook fixed-interval smoother over kf_workers.py:681-721's loop. */
+int kf_smooth_run(kf_batch* handle, int T, double dt, const double* dt_steps, const void* u,
+                  const void* filt_x, const void* filt_P,
+                  void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status, void* stream);
+
 /* Deterministic synthetic GPS+IMU streams for filters
  * [filter_offset, filter_offset + B) of a global population: counter-based Philox4x32-10
  * keyed by seed and the GLOBAL filter index, so any shard regenerates its own slice.

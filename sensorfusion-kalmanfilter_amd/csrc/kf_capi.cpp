@@ -841,6 +841,73 @@ int kf_run(kf_batch* h, int T, double dt, const double* dt_steps, const void* u,
     return launch(h, kfmi::Op::Run, a, stream, "kf_run");
 }
 
+int kf_run_rec(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
+               const uint8_t* mask, int update_every, void* traj, void* cov, void* logdet, void* stream) {
+    const char* fn = "kf_run_rec";
+    if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
+    if (is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_CV2 or KF_MODEL_CV3 handle", fn);
+    if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
+    if (update_every < 1) return fail(KF_EINVAL, "%s: update_every = %d < 1", fn, update_every);
+    if (!dt_steps && !(dt >= 0.0)) return fail(KF_EINVAL, "%s: dt must be >= 0 (got %g)", fn, dt);
+    const int U = T / update_every;
+    if (U > 0 && !z && h->B) return fail(KF_EINVAL, "%s: %d updates need a z stream", fn, U);
+    // the record holds the same-axis entries only: P must be block-diagonal over the axes, and a
+    // diagonal R keeps it so
+    if (!h->r_diag)
+        return fail(KF_EINVAL, "%s: R has a non-zero off-diagonal entry (the covariance record is block-packed)", fn);
+    if (!h->block_p)
+        return fail(KF_EINVAL, "%s: the handle's P is not known to be block-diagonal over the axes (kf_set_state "
+                               "found an entry that couples two axes)", fn);
+    if (int rc = flush_predict(h, stream, fn)) return rc;
+    h->last_predict = false;
+    if (T == 0 || h->B == 0) return KF_OK;
+    kfmi::CvRecArgs a{};
+    a.run = base_args(h);
+    a.run.T = T;
+    a.run.update_every = update_every;
+    a.run.dt = dt;
+    a.run.dt_steps = dt_steps;
+    a.run.u = u;
+    a.run.z = z;
+    a.run.mask = mask;
+    a.run.traj = traj;
+    a.run.logdet = logdet;
+    a.cov = cov;
+    hipError_t e = kfmi::launch_cv_rec(h->axes, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
+int kf_smooth_run(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* filt_x,
+                  const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status, void* stream) {
+    const char* fn = "kf_smooth_run";
+    if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
+    if (is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_CV2 or KF_MODEL_CV3 handle (kf_smooth_sweep smooths "
+                                          "the reference models)", fn);
+    if (h->dtype != KF_F64) return fail(KF_EINVAL, "%s: needs an f64 handle (the f32 smoother is not built)", fn);
+    if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
+    if (!dt_steps && !(dt >= 0.0)) return fail(KF_EINVAL, "%s: dt must be >= 0 (got %g)", fn, dt);
+    if (T == 0 || h->B == 0) return KF_OK;
+    if (!filt_x || !filt_P) return fail(KF_EINVAL, "%s: null filt_x/filt_P", fn);
+    // every row is one [B] descriptor from a 64-bit base, as kf_run's streams: the only span limit
+    // is the row's, B * 8 < 2 GiB, which kf_alloc has enforced; T has no limit of its own
+    kfmi::CvSmoothArgs a{};
+    a.B = h->B;
+    a.T = T;
+    a.dt = dt;
+    a.dt_steps = dt_steps;
+    a.u = u;
+    a.filt_x = filt_x;
+    a.filt_P = filt_P;
+    a.sm_x = sm_x;
+    a.sm_P = sm_P;
+    a.sm_logdet = sm_logdet;
+    a.sm_status = sm_status;
+    a.q_pos = h->params.q_pos;
+    a.q_vel = h->params.q_vel;
+    hipError_t e = kfmi::launch_cv_smooth(h->axes, a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
 int kf_synth(kf_batch* h, uint64_t seed, int64_t filter_offset, int T, double dt, int update_every,
              void* x0_out, void* u_out, void* z_out, void* stream) {
     if (int rc = check_handle(h)) return rc;

@@ -1,0 +1,479 @@
+// gfx950 kernels for a smoothed constant-velocity track (KF_MODEL_CV2 / KF_MODEL_CV3 with a
+// block-diagonal P and a diagonal R): cv_rec_kernel, kf_run's fused run that also records the
+// filtered covariance (kf_run_rec), and cv_smooth_kernel, the Rauch-Tung-Striebel backward pass
+// over that record (kf_smooth_run).
+//
+// Mapping, as in kf_cv.hip: ONE FILTER PER LANE, kBlock lanes per workgroup.  P is block-diagonal
+// over the axes, so a filter is D independent 2-state (pos_i, vel_i) chains: per axis x = (p, v)
+// and P_i = (pp, pv, vv) live in VGPRs, and every record row is one coalesced [B]-long SoA row
+// addressed from a 64-bit base (row_rsrc) plus the lane's 32-bit offset.  Both kernels are bound
+// by HBM bytes at bench sizes; the inputs come through a fully unrolled register ring so the
+// loads of later steps are in flight while a step computes.  No LDS, no atomics, no workspace.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <stdint.h>
+
+#include "kf_common.h"
+#include "kf_internal.h"
+
+namespace kfmi {
+namespace {
+
+using namespace dev;
+
+// Inputs of one forward step (kf_cv.hip's StepIn).
+template <int D, typename T>
+struct RecIn {
+    T u[D];
+    T z[D];
+    uint8_t use;
+};
+
+// ------------------------------------------------------------------------------------
+// kf_run_rec: cv_block_kernel (kf_cv.hip) with the filtered covariance recorded after every
+// step, cov [T][3 D][B], rows 3 i .. 3 i + 2 = axis i's (pp, pv, vv).
+//   THE PREDICT, UPDATE, POISON AND LOG-DET LINES BELOW ARE cv_block_kernel's, REPEATED IN ITS
+//   ORDER.  A change to either copy must be made to both (tests/test_gpu_cv_smoother.py compares
+//   the two with ==).
+// GENERAL = false is cv_block_kernel's input shape (scalar dt, u, no mask).  GENERAL = true: what
+// cv_block_kernel leaves to cv_run_kernel<GENERAL> is decided by wave-uniform branches and
+// zero-length row descriptors, as there: dt_steps (dt, dt^2 / 2 and Q dt per step, from the same
+// expressions), a NULL u (loads return 0) and a mask (a masked lane keeps its prediction).
+// REC_OPT: traj, cov and logdet may each be NULL (stores dropped by the range check; a NULL logdet
+// is not computed and then does not reach the status either, as in cv_run_kernel).
+// State, status, traj and logdet are bit for bit those of the kf_run call with the same inputs
+// and both of its records, on either of its kernels (the block and the general kernel agree on a
+// block-diagonal P).  Which records are NULL never changes a bit here.  It does in kf_run, in
+// fp64: with a record missing it runs cv_run_kernel<GENERAL = true>, whose Q dt is formed in the
+// step and contracted into the sum it enters, one rounding fewer than the hoisted Q dt of the
+// fast shape (see `step` below).
+// ------------------------------------------------------------------------------------
+template <int D, typename T, int DEPTH, bool GENERAL, bool REC_OPT>
+__global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
+    constexpr int N = 2 * D;
+    const CvArgs& a = ra.run;
+    const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (f >= a.B) return;
+    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
+    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
+    const bool has_dts = GENERAL && a.dt_steps != nullptr;
+    const bool has_mask = GENERAL && a.mask != nullptr;
+    const bool has_ld = !REC_OPT || a.logdet != nullptr;
+    T xp[D], xv[D], pp[D], pv[D], vv[D], r[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        xp[i] = ldb<T>(a.x, i, rb, off);
+        xv[i] = ldb<T>(a.x, D + i, rb, off);
+        pp[i] = ldb<T>(a.P, tri<N>(i, i), rb, off);
+        pv[i] = ldb<T>(a.P, tri<N>(i, D + i), rb, off);
+        vv[i] = ldb<T>(a.P, tri<N>(D + i, D + i), rb, off);
+        r[i] = T(a.r[tri<D>(i, i)]);
+    }
+    int32_t st = a.status[f];
+    const int T_ = a.T;
+    const int k_upd = a.update_every;
+    const int U = T_ / k_upd;
+    int ld_upd_step = k_upd - 1;
+    int ld_s = 0;
+    const uint32_t rb_u = (!GENERAL || a.u != nullptr) ? rb : 0u;
+    const uint32_t rb_z = U > 0 ? rb : 0u;
+    const uint32_t rb_tr = (!REC_OPT || a.traj != nullptr) ? rb : 0u;  // absent records: stores dropped
+    const uint32_t rb_cov = (!REC_OPT || ra.cov != nullptr) ? rb : 0u;
+    const uint32_t rb_m = (has_mask && U > 0) ? uint32_t(a.B) : 0u;  // mask rows are [B] bytes
+    const T dt0 = T(a.dt);
+    const T hdt20 = T(0.5) * dt0 * dt0;
+    const T qp0 = T(a.q_pos * a.dt), qv0 = T(a.q_vel * a.dt);
+    auto load_in = [&](int t, RecIn<D, T>& in) {
+        const int tc = t < T_ ? t : T_ - 1;
+        if (tc > ld_upd_step) {
+            ld_upd_step += k_upd;
+            ++ld_s;
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) in.u[i] = ldb_stream(a.u, int64_t(tc) * D + i, rb_u, off, T(0));
+        int s = ld_s < U ? ld_s : U - 1;
+        s = s > 0 ? s : 0;
+        const bool upd = tc == ld_upd_step;  // wave-uniform
+        const uint32_t rbz = upd ? rb_z : 0u;  // z only on update steps
+#pragma unroll
+        for (int i = 0; i < D; ++i) in.z[i] = ldb_stream(a.z, int64_t(s) * D + i, rbz, off, T(0));
+        // a zero-length row (no mask, or no update at this step) loads 0: no branch, no address
+        in.use = GENERAL ? ldb<uint8_t>(a.mask, s, upd ? rb_m : 0u, uint32_t(f)) : uint8_t(1);
+    };
+    int until_upd = k_upd;
+    auto step = [&](int t, const RecIn<D, T>& in) {
+        // GENERAL: cv_run_kernel's per-step dt in its own expressions, statement for statement.  The
+        // shape matters, not only the values: with Q dt formed in the step, next to the sum it
+        // enters, the compiler contracts q dt + P into one fma in fp64 there and here alike
+        // (-ffp-contract=fast), and with Q dt hoisted (cv_block_kernel, GENERAL = false) it does
+        // not; kf_run's two routes differ by that rounding, and each instantiation follows its own
+        T dt = dt0, hdt2 = hdt20, qp = qp0, qv = qv0;
+        if constexpr (GENERAL) {
+            const double dtd = has_dts ? a.dt_steps[t] : a.dt;
+            dt = T(dtd);
+            hdt2 = T(0.5) * dt * dt;
+            qp = T(a.q_pos * dtd);
+            qv = T(a.q_vel * dtd);
+        }
+        // predict (Cv::predict per axis): Bm' = Bm + dt C, A' = A + dt (Bm' + Bm^T), + Q
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            xp[i] = fmaT(hdt2, in.u[i], fmaT(dt, xv[i], xp[i]));
+            xv[i] = fmaT(dt, in.u[i], xv[i]);
+            const T bn = fmaT(dt, vv[i], pv[i]);
+            pp[i] = fmaT(dt, bn + pv[i], pp[i]);
+            pv[i] = bn;
+            pp[i] += qp;
+            vv[i] += qv;
+        }
+        if (--until_upd == 0) {  // wave-uniform
+            until_upd = k_upd;
+            // the mask is per lane: a masked lane computes the update and keeps its old values
+            // (selects, no divergent branch)
+            const bool app = !has_mask || in.use;
+            bool ok = true;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                // sel_update with a diagonal S: one scalar pivot per axis, Joseph form
+                const T S = pp[i] + r[i];
+                ok = ok && (S > T(0));
+                const T dinv = rcp_pos<2>(S);
+                const T k0 = pp[i] * dinv, k1 = pv[i] * dinv;
+                const T y = in.z[i] - xp[i];
+                const T nxp = fmaT(k0, y, xp[i]);
+                const T nxv = fmaT(k1, y, xv[i]);
+                const T e0 = fmaT(k0, S, -pp[i]);
+                const T e1 = fmaT(k1, S, -pv[i]);
+                const T npp = fmaT(e0, k0, fmaT(-k0, pp[i], pp[i]));
+                const T npv = fmaT(e0, k1, fmaT(-k0, pv[i], pv[i]));
+                const T nvv = fmaT(e1, k1, fmaT(-k1, pv[i], vv[i]));
+                // a bad pivot poisons the whole filter, as in the general kernel
+                xp[i] = app ? nxp : xp[i];
+                xv[i] = app ? nxv : xv[i];
+                pp[i] = app ? npp : pp[i];
+                pv[i] = app ? npv : pv[i];
+                vv[i] = app ? nvv : vv[i];
+            }
+            const T poison = ok ? T(0) : quiet_nan<T>();
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                xp[i] = app ? xp[i] + poison : xp[i];
+                xv[i] = app ? xv[i] + poison : xv[i];
+                pp[i] = app ? pp[i] + poison : pp[i];
+                pv[i] = app ? pv[i] + poison : pv[i];
+                vv[i] = app ? vv[i] + poison : vv[i];
+            }
+            st = (ok || !app) ? st : kNotSpd;
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            stb_rec(a.traj, int64_t(t) * N + i, rb_tr, off, xp[i]);
+            stb_rec(a.traj, int64_t(t) * N + D + i, rb_tr, off, xv[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            stb_rec(ra.cov, int64_t(t) * (3 * D) + 3 * i, rb_cov, off, pp[i]);
+            stb_rec(ra.cov, int64_t(t) * (3 * D) + 3 * i + 1, rb_cov, off, pv[i]);
+            stb_rec(ra.cov, int64_t(t) * (3 * D) + 3 * i + 2, rb_cov, off, vv[i]);
+        }
+        if (has_ld) {  // wave-uniform
+            // logdet: LDL pivots in the general 6x6 order (positions, then velocities)
+            T prod = T(1);
+            int ex = 0, e;
+            bool pd = true;
+            T dv[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                pd = pd && (pp[i] > T(0));
+                prod *= pp[i];
+                const T l = pv[i] * rcp_nr<1>(pp[i]);
+                const T v = l * pp[i];
+                dv[i] = fmaT(-l, v, vv[i]);
+            }
+            prod = frexp(prod, &e);
+            ex += e;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                pd = pd && (dv[i] > T(0));
+                prod *= dv[i];
+            }
+            prod = frexp(prod, &e);
+            ex += e;
+            const T ld = pd ? log_mant(prod, ex) : quiet_nan<T>();
+            st = (ld == ld) ? st : kNotSpd;
+            stb_rec(a.logdet, t, rb, off, ld);
+        }
+    };
+    // cv_block_kernel's input ring: DEPTH statically named buffers, prologue drained once
+    RecIn<D, T> buf[DEPTH];
+#pragma unroll
+    for (int j = 0; j < DEPTH - 1; ++j) load_in(j, buf[j]);
+    __builtin_amdgcn_s_waitcnt(0);
+    int t = 0;
+    for (; t + DEPTH <= T_; t += DEPTH) {
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j) {
+            load_in(t + j + DEPTH - 1, buf[(j + DEPTH - 1) % DEPTH]);
+            step(t + j, buf[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DEPTH - 1; ++j)
+        if (t + j < T_) step(t + j, buf[j]);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        stb(a.x, i, rb, off, xp[i]);
+        stb(a.x, D + i, rb, off, xv[i]);
+        stb(a.P, tri<N>(i, i), rb, off, pp[i]);
+        stb(a.P, tri<N>(i, D + i), rb, off, pv[i]);
+        stb(a.P, tri<N>(D + i, D + i), rb, off, vv[i]);
+    }
+    a.status[f] = st;
+}
+
+// ------------------------------------------------------------------------------------
+// kf_smooth_run: the RTS backward pass over filt_x [T][2 D][B] / filt_P [T][3 D][B] (kf_run_rec's
+// traj and cov), f64.  Row T - 1 is the filtered row.  For t = T - 2 .. 0, per axis, with
+// (x_f, P_f) = row t, d = dt[t + 1]:
+//   x_p = F x_f + G u[t + 1], P_p = F P_f F^T + Q d   (cv_rec_kernel's predict lines on row t: the
+//                                                     forward run's P_pred, up to the one rounding
+//                                                     of Q d + P that its two input shapes differ by)
+//   C = (P_f F^T) P_p^-1                              (2 x 2 LDL^T of P_p in-lane; its two pivots'
+//                                                     reciprocals are IEEE divisions, as in
+//                                                     ref_smooth_kernel: P_f - C P_p C^T cancels)
+//   x_s[t] = x_f + C (x_s[t + 1] - x_p)
+//   P_s[t] = P_f + C (P_s[t + 1] - P_p) C^T           (once per packed entry)
+// The lane carries the smoothed row t + 1, 5 values per axis.  The inputs of row t (2 D states,
+// 3 D covariance entries, D controls) come backwards through a ring of DEPTH statically named
+// buffers: backward step s is row t = T - 2 - s, loaded DEPTH - 1 steps before step s runs and so
+// before the only store that can overwrite it (the lane's own store of row t in step s), which
+// makes sm_x == filt_x / sm_P == filt_P equal to running out of place.
+// A NaN in a loaded row (state, covariance or control) or a non-positive pivot of P_p poisons the
+// filter from that t down to 0: NaN rows, KF_ENOTSPD in sm_status; the rows above are stored.
+// sm_logdet takes the LDL pivots of P_s in the forward log-det's order and form.
+// ------------------------------------------------------------------------------------
+#ifndef KF_CV_SMOOTH_DEPTH
+#define KF_CV_SMOOTH_DEPTH 4
+#endif
+constexpr int kCvSmoothDepth = KF_CV_SMOOTH_DEPTH;  // input ring of cv_smooth_kernel
+
+template <int D>
+struct SmoothRow {
+    double x[2 * D];
+    double P[3 * D];
+    double u[D];
+};
+
+template <int D, int DEPTH>
+__global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const CvSmoothArgs a) {
+    using T = double;
+    constexpr int N = 2 * D, NP = 3 * D;
+    const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (f >= a.B) return;
+    const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
+    const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
+    const bool has_dts = a.dt_steps != nullptr;
+    const bool need_ld = a.sm_logdet != nullptr;
+    const uint32_t rb_u = a.u != nullptr ? rb : 0u;      // no control: loads return 0
+    const uint32_t rb_sx = a.sm_x != nullptr ? rb : 0u;  // absent outputs: stores dropped
+    const uint32_t rb_sP = a.sm_P != nullptr ? rb : 0u;
+    const int T_ = a.T;
+
+    T sp[D], sv[D], spp[D], spv[D], svv[D];  // the smoothed row t + 1
+    int32_t st = 0;
+    auto poison = [&]() {
+        st = kNotSpd;
+#pragma unroll
+        for (int i = 0; i < D; ++i) sp[i] = sv[i] = spp[i] = spv[i] = svv[i] = quiet_nan<T>();
+    };
+    auto store_row = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            stb_rec(a.sm_x, int64_t(t) * N + i, rb_sx, off, sp[i]);
+            stb_rec(a.sm_x, int64_t(t) * N + D + i, rb_sx, off, sv[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            stb_rec(a.sm_P, int64_t(t) * NP + 3 * i, rb_sP, off, spp[i]);
+            stb_rec(a.sm_P, int64_t(t) * NP + 3 * i + 1, rb_sP, off, spv[i]);
+            stb_rec(a.sm_P, int64_t(t) * NP + 3 * i + 2, rb_sP, off, svv[i]);
+        }
+        if (need_ld) {  // wave-uniform
+            // cv_rec_kernel's log-det lines on P_s: positions, renormalise, velocities, renormalise
+            T prod = T(1);
+            int ex = 0, e;
+            bool pd = true;
+            T dv[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                pd = pd && (spp[i] > T(0));
+                prod *= spp[i];
+                const T l = spv[i] * rcp_nr<1>(spp[i]);
+                const T v = l * spp[i];
+                dv[i] = fmaT(-l, v, svv[i]);
+            }
+            prod = frexp(prod, &e);
+            ex += e;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                pd = pd && (dv[i] > T(0));
+                prod *= dv[i];
+            }
+            prod = frexp(prod, &e);
+            ex += e;
+            const T ld = pd ? log_mant(prod, ex) : quiet_nan<T>();
+            stb_rec(a.sm_logdet, t, rb, off, ld);
+        }
+    };
+    auto load_xP = [&](int t, T (&x)[N], T (&P)[NP]) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = ldb_stream(a.filt_x, int64_t(t) * N + i, rb, off, T(0));
+#pragma unroll
+        for (int k = 0; k < NP; ++k) P[k] = ldb_stream(a.filt_P, int64_t(t) * NP + k, rb, off, T(0));
+    };
+
+    // row T - 1: the filtered row itself
+    {
+        T x[N], P[NP];
+        load_xP(T_ - 1, x, P);
+        __builtin_amdgcn_s_waitcnt(0);
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) nan = nan || x[i] != x[i];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) nan = nan || P[k] != P[k];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            sp[i] = x[i];
+            sv[i] = x[D + i];
+            spp[i] = P[3 * i];
+            spv[i] = P[3 * i + 1];
+            svv[i] = P[3 * i + 2];
+        }
+        if (nan) poison();
+        store_row(T_ - 1);
+    }
+
+    const int n = T_ - 1;  // backward steps; step s is row t = T - 2 - s (past the end: row 0 again)
+    if (n > 0) {
+        T dt = T(a.dt);
+        T hdt2 = T(0.5) * dt * dt;
+        T qp = T(a.q_pos * a.dt), qv = T(a.q_vel * a.dt);
+        auto load = [&](int s, SmoothRow<D>& in) {
+            const int t = T_ - 2 - (s < n ? s : n - 1);
+            load_xP(t, in.x, in.P);
+#pragma unroll
+            for (int i = 0; i < D; ++i) in.u[i] = ldb_stream(a.u, int64_t(t + 1) * D + i, rb_u, off, T(0));
+        };
+        auto step = [&](int s, const SmoothRow<D>& in) {
+            const int t = T_ - 2 - s;
+            if (has_dts) {  // wave-uniform: the forward step t + 1's dt, in its expressions
+                const double dtd = a.dt_steps[t + 1];
+                dt = T(dtd);
+                hdt2 = T(0.5) * dt * dt;
+                qp = T(a.q_pos * dtd);
+                qv = T(a.q_vel * dtd);
+            }
+            bool bad = false;
+#pragma unroll
+            for (int i = 0; i < N; ++i) bad = bad || in.x[i] != in.x[i];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) bad = bad || in.P[k] != in.P[k];
+#pragma unroll
+            for (int i = 0; i < D; ++i) bad = bad || in.u[i] != in.u[i];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                const T fx = in.x[i], fv = in.x[D + i];
+                const T fpp = in.P[3 * i], fpv = in.P[3 * i + 1], fvv = in.P[3 * i + 2];
+                // predict: cv_rec_kernel's lines on the filtered row
+                const T px = fmaT(hdt2, in.u[i], fmaT(dt, fv, fx));
+                const T pvx = fmaT(dt, in.u[i], fv);
+                const T bn = fmaT(dt, fvv, fpv);
+                T ppp = fmaT(dt, bn + fpv, fpp);
+                ppp += qp;
+                const T ppv = bn;
+                const T pvv = fvv + qv;
+                // P_f F^T = [[fpp + dt fpv, fpv], [fpv + dt fvv, fvv]]
+                const T a00 = fmaT(dt, fpv, fpp);
+                // P_p = L D L^T (unit lower L); the two pivots are divided by exactly
+                const T d0 = ppp;
+                const T i0 = T(1) / d0;
+                const T l10 = ppv * i0;
+                const T v0 = l10 * d0;
+                const T d1 = fmaT(-l10, v0, pvv);
+                const T i1 = T(1) / d1;
+                bad = bad || !(d0 > T(0) && d1 > T(0));
+                // C row r solves P_p c = (row r of P_f F^T)^T
+                const T w01 = fmaT(-l10, a00, fpv);
+                const T c01 = w01 * i1;
+                const T c00 = fmaT(-l10, c01, a00 * i0);
+                const T w11 = fmaT(-l10, bn, fvv);
+                const T c11 = w11 * i1;
+                const T c10 = fmaT(-l10, c11, bn * i0);
+                const T dx0 = sp[i] - px, dx1 = sv[i] - pvx;
+                const T D00 = spp[i] - ppp, D01 = spv[i] - ppv, D11 = svv[i] - pvv;
+                sp[i] = fmaT(c01, dx1, fmaT(c00, dx0, fx));
+                sv[i] = fmaT(c11, dx1, fmaT(c10, dx0, fv));
+                const T cd00 = fmaT(c01, D01, c00 * D00), cd01 = fmaT(c01, D11, c00 * D01);
+                const T cd10 = fmaT(c11, D01, c10 * D00), cd11 = fmaT(c11, D11, c10 * D01);
+                spp[i] = fmaT(cd01, c01, fmaT(cd00, c00, fpp));
+                spv[i] = fmaT(cd01, c11, fmaT(cd00, c10, fpv));
+                svv[i] = fmaT(cd11, c11, fmaT(cd10, c10, fvv));
+            }
+            if (bad || st != 0) poison();
+            store_row(t);
+        };
+        SmoothRow<D> buf[DEPTH];
+#pragma unroll
+        for (int j = 0; j < DEPTH - 1; ++j) load(j, buf[j]);
+        __builtin_amdgcn_s_waitcnt(0);
+        int s = 0;
+        for (; s + DEPTH <= n; s += DEPTH) {
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j) {
+                load(s + j + DEPTH - 1, buf[(j + DEPTH - 1) % DEPTH]);
+                step(s + j, buf[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DEPTH - 1; ++j)
+            if (s + j < n) step(s + j, buf[j]);
+    }
+    if (a.sm_status) a.sm_status[f] = st;
+}
+
+template <int D, typename T>
+void launch_rec_t(const CvRecArgs& a, dim3 grid, hipStream_t st) {
+    // the inputs alone choose the arithmetic's form (GENERAL), never which records are asked for
+    const bool general = a.run.dt_steps != nullptr || a.run.u == nullptr || a.run.mask != nullptr;
+    const bool all_rec = a.run.traj != nullptr && a.cov != nullptr && a.run.logdet != nullptr;
+    if (general) cv_rec_kernel<D, T, 8, true, true><<<grid, kBlock, 0, st>>>(a);
+    else if (all_rec) cv_rec_kernel<D, T, 8, false, false><<<grid, kBlock, 0, st>>>(a);
+    else cv_rec_kernel<D, T, 8, false, true><<<grid, kBlock, 0, st>>>(a);
+}
+
+}  // namespace
+
+hipError_t launch_cv_rec(int axes, bool f64, const CvRecArgs& a, hipStream_t stream) {
+    if (a.run.B <= 0 || a.run.T <= 0 || (axes != 2 && axes != 3)) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.run.B + kBlock - 1) / kBlock));
+    if (axes == 2) {
+        if (f64) launch_rec_t<2, double>(a, grid, stream);
+        else launch_rec_t<2, float>(a, grid, stream);
+    } else {
+        if (f64) launch_rec_t<3, double>(a, grid, stream);
+        else launch_rec_t<3, float>(a, grid, stream);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cv_smooth(int axes, const CvSmoothArgs& a, hipStream_t stream) {
+    if (a.B <= 0 || a.T <= 0 || (axes != 2 && axes != 3) || !a.filt_x || !a.filt_P) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+    if (axes == 2) cv_smooth_kernel<2, kCvSmoothDepth><<<grid, kBlock, 0, stream>>>(a);
+    else cv_smooth_kernel<3, kCvSmoothDepth><<<grid, kBlock, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace kfmi

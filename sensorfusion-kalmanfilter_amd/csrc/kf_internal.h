@@ -32,6 +32,30 @@ struct CvArgs {
     int blocks_per_cu;       // 2..8: cap resident workgroups per CU (KF_OPT_BLOCKS_PER_CU); 0 = none
 };
 
+// kf_run_rec (cv_rec_kernel, kf_cv_smooth.hip): kf_run's arguments and the covariance record.
+// CvArgs itself stays as it is: it is the argument block of kf_cv.hip's kernels.
+struct CvRecArgs {
+    CvArgs run;              // as kf_run fills it (block_p, prefetch_depth and blocks_per_cu are not read)
+    void* cov;               // [T][3 axes][B]: axis i's (pp, pv, vv) in rows 3 i .. 3 i + 2, or nullptr
+};
+
+// kf_smooth_run (cv_smooth_kernel, kf_cv_smooth.hip): the RTS backward pass over a kf_run_rec
+// record, f64.  Every output may be nullptr.
+struct CvSmoothArgs {
+    int64_t B;
+    int T;
+    double dt;               // scalar dt (used when dt_steps == nullptr)
+    const double* dt_steps;  // [T] the forward run's per-step dt, or nullptr
+    const void* u;           // [T][axes][B] the forward run's control, or nullptr (zero control)
+    const void* filt_x;      // [T][2 axes][B]
+    const void* filt_P;      // [T][3 axes][B]
+    void* sm_x;              // [T][2 axes][B]; may be filt_x
+    void* sm_P;              // [T][3 axes][B]; may be filt_P
+    void* sm_logdet;         // [T][B]
+    int32_t* sm_status;      // [B]
+    double q_pos, q_vel;     // Q = diag(q_pos dt, q_vel dt)
+};
+
 struct SynthArgs {
     int64_t B;
     int64_t filter_offset;
@@ -511,6 +535,10 @@ hipError_t launch_cv(int axes, bool f64, Op op, const CvArgs& a, hipStream_t str
 // *flag |= 1 if any filter's P couples different axes (flag: device int, zeroed by the caller).
 hipError_t launch_cv_offblock(int axes, bool f64, const CvArgs& a, int* flag, hipStream_t stream);
 hipError_t launch_synth(int axes, bool f64, const SynthArgs& a, hipStream_t stream);
+// kf_cv_smooth.hip: the fused run with the covariance record (block-diagonal P, diagonal R: the
+// caller has checked both), and the RTS backward pass over such a record (f64 only)
+hipError_t launch_cv_rec(int axes, bool f64, const CvRecArgs& a, hipStream_t stream);
+hipError_t launch_cv_smooth(int axes, const CvSmoothArgs& a, hipStream_t stream);
 // bytes (a multiple of 4) from src to dst on the stream, by a kernel
 hipError_t launch_copy(void* dst, const void* src, size_t bytes, hipStream_t stream);
 // chain = true: the chain-parallel kernel (kGroup lanes per filter), for few filters.

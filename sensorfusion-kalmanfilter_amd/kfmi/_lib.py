@@ -119,6 +119,8 @@ SIGNATURES = {
     'kf_predict': (_i, [_vp, _d, _vp, _vp, _vp, _vp]),
     'kf_update': (_i, [_vp, _vp, _vp, _vp, _vp]),
     'kf_run': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'kf_run_rec': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'kf_smooth_run': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kf_synth': (_i, [_vp, ctypes.c_uint64, _i64, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'kf_run_events': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),
     'kf_run_events_seq': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),

@@ -92,6 +92,8 @@ assert len(SCORE_ROWS) == _lib.KF_SCORE_ROWS
 
 SweepScores = collections.namedtuple('SweepScores', 'scores n_updated traj logdet updated ckpt_x ckpt_P')
 SmoothedSweep = collections.namedtuple('SmoothedSweep', 'x P traj logdet status')
+SmoothedRun = collections.namedtuple('SmoothedRun', 'x P logdet status')
+RunSmoothed = collections.namedtuple('RunSmoothed', 'traj cov logdet smoothed')
 
 
 def innovation_nll(scores, model, sensor):
@@ -338,6 +340,83 @@ class BatchedKF:
         check(_lib.lib().kf_run(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(zd),
                                 _ptr(md), int(update_every), _ptr(tr), _ptr(ld), self._stream()))
         return tr, ld
+
+    def _need_cv(self, what):
+        if self.model in REF_MODELS:
+            raise KFError(_lib.KF_EINVAL, f'{what}: needs a cv2 or cv3 handle')
+
+    def run_rec(self, u, z, dt=None, dt_steps=None, update_every=1, mask=None, traj=True, cov=True, logdet=True):
+        """``run`` that also records the filtered covariance (kf_run_rec): the forward half of a
+        smoothed track.  u [T, c, B] or None (zero control; then z, dt_steps or mask give T:
+        T = len(dt_steps), else update_every * len(z)); the other arguments as in ``run``.
+        Returns (traj [T, n, B], cov [T, 3 d, B], logdet [T, B]), None where not asked for; rows
+        3 i .. 3 i + 2 of cov[t] are axis i's (pp, pv, vv) after step t.  State, status, traj and
+        logdet are ``run``'s bit for bit.  KFError(KF_EINVAL) unless the handle's P is
+        block-diagonal over the axes and R is diagonal."""
+        self._need_cv('run_rec')
+        if u is not None:
+            T = int(u.shape[0])
+        elif dt_steps is not None:
+            T = int(dt_steps.shape[0])
+        else:
+            T = int(z.shape[0]) * int(update_every)
+        U = T // update_every
+        ud = self._dev(u, (T, self.c, self.batch), 'u') if u is not None else None
+        zd = self._dev(z, (U, self.m, self.batch), 'z') if U > 0 else None
+        md = self._dev(mask, (U, self.batch), 'mask', torch.uint8) if mask is not None else None
+        dts = self._dev(dt_steps, (T,), 'dt_steps', torch.float64) if dt_steps is not None else None
+        if dts is None and dt is None:
+            raise ValueError('run_rec: give dt (scalar) or dt_steps [T]')
+        tr = self.empty(T, self.n, self.batch) if traj else None
+        cv = self.empty(T, 3 * self.c, self.batch) if cov else None
+        ld = self.empty(T, self.batch) if logdet else None
+        check(_lib.lib().kf_run_rec(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(zd), _ptr(md),
+                                    int(update_every), _ptr(tr), _ptr(cv), _ptr(ld), self._stream()))
+        return tr, cv, ld
+
+    def smooth_run(self, filt_x, filt_P, u=None, dt=None, dt_steps=None, x=True, P=False, logdet=False, status=True,
+                   inplace=False):
+        """The RTS smoother over a ``run_rec`` record (kf_smooth_run): filt_x [T, n, B] its traj,
+        filt_P [T, 3 d, B] its cov (device tensors or arrays); u, dt / dt_steps the forward run's
+        (u None: zero control).  An f64 cv2 / cv3 handle, whose state and status are not touched.
+        Returns SmoothedRun(x [T, n, B], P [T, 3 d, B], logdet [T, B], status [B] int32), None where
+        not asked for; row T - 1 is the filtered row.  ``inplace``: x and P (where asked for)
+        overwrite filt_x / filt_P, which must then be contiguous device tensors.  A filter whose
+        record is not positive definite (or holds a NaN) has NaN rows from there down to 0 and
+        KF_ENOTSPD in ``status``."""
+        self._need_cv('smooth_run')
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'smooth_run: needs an f64 handle')
+        T = int(filt_x.shape[0])
+        if inplace and not (torch.is_tensor(filt_x) and torch.is_tensor(filt_P) and filt_x.device == self.device
+                            and filt_P.device == self.device and filt_x.is_contiguous() and filt_P.is_contiguous()
+                            and filt_x.dtype == self.torch_dtype and filt_P.dtype == self.torch_dtype):
+            raise KFError(_lib.KF_EINVAL, 'smooth_run: inplace needs contiguous float64 device tensors filt_x / filt_P')
+        fx = self._dev(filt_x, (T, self.n, self.batch), 'filt_x')
+        fP = self._dev(filt_P, (T, 3 * self.c, self.batch), 'filt_P')
+        ud = self._dev(u, (T, self.c, self.batch), 'u') if u is not None else None
+        dts = self._dev(dt_steps, (T,), 'dt_steps', torch.float64) if dt_steps is not None else None
+        if dts is None and dt is None:
+            raise ValueError('smooth_run: give dt (scalar) or dt_steps [T]')
+        sx = (fx if inplace else self.empty(T, self.n, self.batch)) if x else None
+        sP = (fP if inplace else self.empty(T, 3 * self.c, self.batch)) if P else None
+        ld = self.empty(T, self.batch) if logdet else None
+        st = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if status else None
+        check(_lib.lib().kf_smooth_run(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(fx), _ptr(fP),
+                                       _ptr(sx), _ptr(sP), _ptr(ld), _ptr(st), self._stream()))
+        return SmoothedRun(sx, sP, ld, st)
+
+    def run_smoothed(self, u, z, dt=None, dt_steps=None, update_every=1, mask=None, logdet=True, P=False,
+                     smoothed_logdet=False):
+        """``run_rec`` then ``smooth_run`` out of place: RunSmoothed(traj, cov, logdet, smoothed), the
+        filtered track, covariance record and log det, and ``smoothed`` = SmoothedRun(x, P, logdet,
+        status).  An f64 cv2 / cv3 handle."""
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'run_smoothed: needs an f64 handle')
+        tr, cv, ld = self.run_rec(u, z, dt=dt, dt_steps=dt_steps, update_every=update_every, mask=mask,
+                                  logdet=logdet)
+        sm = self.smooth_run(tr, cv, u=u, dt=dt, dt_steps=dt_steps, P=P, logdet=smoothed_logdet)
+        return RunSmoothed(tr, cv, ld, sm)
 
     def run_host(self, u, z, dt, update_every=1, chunks=8, traj=None, logdet=None):
         """``run`` for streams that live in host memory (numpy arrays or CPU tensors, the shapes
