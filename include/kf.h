@@ -367,6 +367,70 @@ int kf_smooth_run(kf_batch* handle, int T, double dt, const double* dt_steps, co
                   const void* filt_x, const void* filt_P,
                   void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status, void* stream);
 
+/* Rows of the constant-velocity models' per-filter constant table (kf_run_scores,
+ * kf_smooth_run_params): device [KF_CV_CONST_ROWS(d)][B] double, filter index fastest, d = 2 | 3
+ * axes.  Column f stands in for the handle's kf_params in filter f: q_pos, q_vel, then the diagonal
+ * R entry of each axis.  P0 is not part of it (the handle's state is whatever it holds). */
+#define KF_CV_CONST_Q_POS    0
+#define KF_CV_CONST_Q_VEL    1
+#define KF_CV_CONST_R        2   /* + axis */
+#define KF_CV_CONST_ROWS(d)  (2 + (d))
+
+/* kf_run_rec under per-filter noise constants, scored in the launch that runs the filters: what
+ * kf_run_sweep_params / kf_run_sweep_scores are to the reference models, for KF_MODEL_CV2 /
+ * KF_MODEL_CV3 in both dtypes, one filter per lane.  Every argument it shares with kf_run_rec means
+ * what it means there (dt / dt_steps, NULL u, mask, update_every, the record layouts, each record
+ * may be NULL, a held-back kf_predict runs first), and its KF_EINVAL cases are kf_run_rec's, all
+ * before anything is queued; further ones: track given with scores NULL.  With consts given the
+ * handle's own R is not read and need not be diagonal.
+ *
+ * consts: the table above, or NULL = the handle's constants.  Caller-owned until the launch has
+ * run.  Each value is converted exactly as the handle's own is: T(q * dt) formed in double, T(r).
+ * The table lives on the device, so its values are not validated: a set that makes an innovation
+ * pivot non-positive, or a log det NaN, fails that filter alone (KF_ENOTSPD, NaN from there on), as
+ * any filter of kf_run fails.
+ *
+ * scores: device [KF_SCORE_ROWS][B] double in the KF_SCORE_* layout, overwritten, or NULL.
+ *   KF_SCORE_IMU_*: 0.
+ *   KF_SCORE_GPS_N: the fixes the filter applied (an update step whose mask entry is non-zero, or
+ *   any update step with mask NULL).
+ *   KF_SCORE_GPS_NIS: the sum over them of sum_axis y^2 / S, y = z - x_pred and S = pp_pred + r the
+ *   update's own values and 1 / S the reciprocal it computes anyway; each axis' term is converted to
+ *   double and added in step order, axes in order.
+ *   KF_SCORE_GPS_LOGDET_S: the log of the product of every applied S, kept as a running
+ *   mantissa-exponent pair in double and logged once at the end (as kf_run_sweep_scores does).
+ *   KF_SCORE_POS_N / KF_SCORE_POS_SSE: against track, device [T][d][B] in the handle's dtype, or
+ *   NULL (both rows 0).  Step t is scored after the step, its update included, when none of the
+ *   filter's d track values at t is NaN: position and track value are converted to double, then
+ *   differenced, squared and summed.
+ *   A filter whose status is not KF_OK when the launch ends has NaN in the three float rows (NIS,
+ *   LOGDET_S, SSE); its counts still count.  T = 0 zeroes the table.
+ * kfmi.innovation_nll(scores, 'cv2' | 'cv3', 'gps') turns the GPS rows into the Gaussian
+ * innovation negative log-likelihood.
+ *
+ * Bit for bit: state, status, traj, cov and logdet do not depend on whether scores / track are
+ * given nor on which records are NULL; with consts NULL they are kf_run_rec's; with consts, column
+ * f's are those of kf_run_rec on a handle whose kf_params hold column f's values.  A filter's
+ * scores do not depend on B, its place in its wave, the records or its neighbours: everything is
+ * lane-local, no atomics, no reduction.  scores NULL with consts NULL is kf_run_rec itself.
+ * Asynchronous on `stream`, capturable, allocates nothing.  The reference has no per-filter
+ * constants and no innovation statistics for this loop (kf_workers.py:681-721). */
+int kf_run_scores(kf_batch* handle, int T, double dt, const double* dt_steps, const void* u,
+                  const void* z, const uint8_t* mask, int update_every,
+                  const double* consts, const void* track, double* scores,
+                  void* traj, void* cov, void* logdet, void* stream);
+
+/* kf_smooth_run under the per-filter Q of kf_run_scores' table: filter f's backward pass forms
+ * P_p with column f's q_pos and q_vel (rows KF_CV_CONST_Q_POS / KF_CV_CONST_Q_VEL; the R rows are
+ * not read), so a record of kf_run_scores(consts) is smoothed under the constants it was filtered
+ * with.  consts NULL is kf_smooth_run.  Everything else is kf_smooth_run's: f64 only, in place if
+ * asked, failure per filter, T = 0 and T = 1, its KF_EINVAL cases.  Bit for bit: column f's rows
+ * are those of kf_smooth_run on a handle holding column f's q. */
+int kf_smooth_run_params(kf_batch* handle, int T, double dt, const double* dt_steps, const void* u,
+                         const void* filt_x, const void* filt_P,
+                         void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status,
+                         const double* consts, void* stream);
+
 /* Deterministic synthetic GPS+IMU streams for filters
  * [filter_offset, filter_offset + B) of a global population: counter-based Philox4x32-10
  * keyed by seed and the GLOBAL filter index, so any shard regenerates its own slice.

@@ -841,9 +841,13 @@ int kf_run(kf_batch* h, int T, double dt, const double* dt_steps, const void* u,
     return launch(h, kfmi::Op::Run, a, stream, "kf_run");
 }
 
-int kf_run_rec(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
-               const uint8_t* mask, int update_every, void* traj, void* cov, void* logdet, void* stream) {
-    const char* fn = "kf_run_rec";
+namespace {
+
+// kf_run_rec and kf_run_scores (fn names the caller): consts, track and scores all nullptr is
+// kf_run_rec's own launch
+int run_rec_impl(const char* fn, kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
+                 const uint8_t* mask, int update_every, const double* consts, const void* track, double* scores,
+                 void* traj, void* cov, void* logdet, void* stream) {
     if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
     if (is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_CV2 or KF_MODEL_CV3 handle", fn);
     if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
@@ -851,16 +855,23 @@ int kf_run_rec(kf_batch* h, int T, double dt, const double* dt_steps, const void
     if (!dt_steps && !(dt >= 0.0)) return fail(KF_EINVAL, "%s: dt must be >= 0 (got %g)", fn, dt);
     const int U = T / update_every;
     if (U > 0 && !z && h->B) return fail(KF_EINVAL, "%s: %d updates need a z stream", fn, U);
+    if (track && !scores) return fail(KF_EINVAL, "%s: a track needs a scores table to be scored into", fn);
     // the record holds the same-axis entries only: P must be block-diagonal over the axes, and a
-    // diagonal R keeps it so
-    if (!h->r_diag)
+    // diagonal R keeps it so (a consts table brings its own diagonal R: the handle's is not read)
+    if (!consts && !h->r_diag)
         return fail(KF_EINVAL, "%s: R has a non-zero off-diagonal entry (the covariance record is block-packed)", fn);
     if (!h->block_p)
         return fail(KF_EINVAL, "%s: the handle's P is not known to be block-diagonal over the axes (kf_set_state "
                                "found an entry that couples two axes)", fn);
     if (int rc = flush_predict(h, stream, fn)) return rc;
     h->last_predict = false;
-    if (T == 0 || h->B == 0) return KF_OK;
+    if (h->B == 0) return KF_OK;
+    if (T == 0) {
+        if (!scores) return KF_OK;
+        hipError_t e = hipMemsetAsync(scores, 0, sizeof(double) * KF_SCORE_ROWS * static_cast<size_t>(h->B),
+                                      static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+    }
     kfmi::CvRecArgs a{};
     a.run = base_args(h);
     a.run.T = T;
@@ -873,13 +884,42 @@ int kf_run_rec(kf_batch* h, int T, double dt, const double* dt_steps, const void
     a.run.traj = traj;
     a.run.logdet = logdet;
     a.cov = cov;
-    hipError_t e = kfmi::launch_cv_rec(h->axes, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream));
+    hipError_t e;
+    if (!consts && !scores) {
+        e = kfmi::launch_cv_rec(h->axes, h->dtype == KF_F64, a, static_cast<hipStream_t>(stream));
+    } else {
+        kfmi::CvScoreArgs sa{};
+        sa.rec = a;
+        sa.consts = consts;
+        sa.track = track;
+        sa.scores = scores;
+        e = kfmi::launch_cv_scores(h->axes, h->dtype == KF_F64, sa, static_cast<hipStream_t>(stream));
+    }
     return e == hipSuccess ? KF_OK : hip_fail(e, fn);
 }
 
-int kf_smooth_run(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* filt_x,
-                  const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status, void* stream) {
-    const char* fn = "kf_smooth_run";
+}  // namespace
+
+int kf_run_rec(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
+               const uint8_t* mask, int update_every, void* traj, void* cov, void* logdet, void* stream) {
+    return run_rec_impl("kf_run_rec", h, T, dt, dt_steps, u, z, mask, update_every, nullptr, nullptr, nullptr, traj,
+                        cov, logdet, stream);
+}
+
+int kf_run_scores(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
+                  const uint8_t* mask, int update_every, const double* consts, const void* track, double* scores,
+                  void* traj, void* cov, void* logdet, void* stream) {
+    return run_rec_impl("kf_run_scores", h, T, dt, dt_steps, u, z, mask, update_every, consts, track, scores, traj,
+                        cov, logdet, stream);
+}
+
+namespace {
+
+// kf_smooth_run and kf_smooth_run_params (fn names the caller): consts = nullptr is kf_smooth_run's
+// own launch
+int smooth_run_impl(const char* fn, kf_batch* h, int T, double dt, const double* dt_steps, const void* u,
+                    const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet,
+                    int32_t* sm_status, const double* consts, void* stream) {
     if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
     if (is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_CV2 or KF_MODEL_CV3 handle (kf_smooth_sweep smooths "
                                           "the reference models)", fn);
@@ -904,8 +944,31 @@ int kf_smooth_run(kf_batch* h, int T, double dt, const double* dt_steps, const v
     a.sm_status = sm_status;
     a.q_pos = h->params.q_pos;
     a.q_vel = h->params.q_vel;
-    hipError_t e = kfmi::launch_cv_smooth(h->axes, a, static_cast<hipStream_t>(stream));
+    hipError_t e;
+    if (!consts) {
+        e = kfmi::launch_cv_smooth(h->axes, a, static_cast<hipStream_t>(stream));
+    } else {
+        kfmi::CvSmoothParamArgs pa{};
+        pa.smooth = a;
+        pa.consts = consts;
+        e = kfmi::launch_cv_smooth_params(h->axes, pa, static_cast<hipStream_t>(stream));
+    }
     return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
+}  // namespace
+
+int kf_smooth_run(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* filt_x,
+                  const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status, void* stream) {
+    return smooth_run_impl("kf_smooth_run", h, T, dt, dt_steps, u, filt_x, filt_P, sm_x, sm_P, sm_logdet, sm_status,
+                           nullptr, stream);
+}
+
+int kf_smooth_run_params(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* filt_x,
+                         const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status,
+                         const double* consts, void* stream) {
+    return smooth_run_impl("kf_smooth_run_params", h, T, dt, dt_steps, u, filt_x, filt_P, sm_x, sm_P, sm_logdet,
+                           sm_status, consts, stream);
 }
 
 int kf_synth(kf_batch* h, uint64_t seed, int64_t filter_offset, int T, double dt, int update_every,

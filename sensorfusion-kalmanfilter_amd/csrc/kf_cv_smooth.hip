@@ -1,7 +1,9 @@
 // gfx950 kernels for a smoothed constant-velocity track (KF_MODEL_CV2 / KF_MODEL_CV3 with a
 // block-diagonal P and a diagonal R): cv_rec_kernel, kf_run's fused run that also records the
 // filtered covariance (kf_run_rec), and cv_smooth_kernel, the Rauch-Tung-Striebel backward pass
-// over that record (kf_smooth_run).
+// over that record (kf_smooth_run).  Template flags of the same two kernels give every filter its
+// own q_pos, q_vel and R and score the run where it runs (kf_run_scores), and smooth under the same
+// per-filter Q (kf_smooth_run_params).
 //
 // Mapping, as in kf_cv.hip: ONE FILTER PER LANE, kBlock lanes per workgroup.  P is block-diagonal
 // over the axes, so a filter is D independent 2-state (pos_i, vel_i) chains: per axis x = (p, v)
@@ -13,6 +15,8 @@
 #include <math.h>
 
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "kf_common.h"
 #include "kf_internal.h"
@@ -29,6 +33,27 @@ struct RecIn {
     T z[D];
     uint8_t use;
 };
+// SCORED: the step's track row rides in the ring with its other inputs
+template <int D, typename T>
+struct RecInScored : RecIn<D, T> {
+    T tr[D];
+};
+
+// SCORED: a lane's score accumulators (kf_run_scores).  Doubles whatever the handle's dtype; the
+// product of every applied S is a running (mantissa, binary exponent) pair, logged once at the end
+// (kf_ref_chainlane.h's ScoreAcc, one filter per lane)
+struct CvScoreAcc {
+    int32_t ngps = 0;   // applied fixes
+    double nis = 0.0;   // sum over them of sum_axis y^2 / S
+    double ldm = 1.0;   // product of their S: mantissa ...
+    int32_t lde = 0;    // ... and binary exponent
+    int32_t npos = 0;   // steps scored against the track
+    double sse = 0.0;   // sum over them of sum_axis (pos - track)^2
+};
+struct NoCvScore {};
+
+__device__ __forceinline__ const CvRecArgs& rec_args(const CvRecArgs& a) { return a; }
+__device__ __forceinline__ const CvRecArgs& rec_args(const CvScoreArgs& a) { return a.rec; }
 
 // ------------------------------------------------------------------------------------
 // kf_run_rec: cv_block_kernel (kf_cv.hip) with the filtered covariance recorded after every
@@ -48,10 +73,25 @@ struct RecIn {
 // fp64: with a record missing it runs cv_run_kernel<GENERAL = true>, whose Q dt is formed in the
 // step and contracted into the sum it enters, one rounding fewer than the hoisted Q dt of the
 // fast shape (see `step` below).
+// PARAMS / SCORED (kf_run_scores; the argument block is then CvScoreArgs, A): everything they add
+// sits under `if constexpr`, and the instantiations without them are instruction for instruction
+// what they were (profiles/cv_scores/isa_compare.log).
+// PARAMS: q_pos, q_vel and the diagonal of R are the lane's column of ka.consts, loaded once before
+// the first step (a NULL table: the handle's, by a wave-uniform select); each enters the
+// expressions the handle's own constant enters, T(q * dt) formed in double where each shape forms
+// it, so either shape keeps its own rounding of Q dt + P and column f is kf_run_rec on a handle
+// holding column f's values, bit for bit.
+// SCORED: lane-local accumulators, no atomics and no reduction.  The update's own y, S and 1 / S
+// give the NIS and the running product of S (a masked lane adds 0 and multiplies by 1); the track
+// row of step t comes through the ring and is scored after the step unless one of its D values is
+// NaN.  A NULL track or a NULL scores table costs nothing but the arithmetic: zero-length rows.
 // ------------------------------------------------------------------------------------
-template <int D, typename T, int DEPTH, bool GENERAL, bool REC_OPT>
-__global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
+template <int D, typename T, int DEPTH, bool GENERAL, bool REC_OPT, bool PARAMS = false, bool SCORED = false,
+          typename A = CvRecArgs>
+__global__ __launch_bounds__(kBlock) void cv_rec_kernel(const A ka) {
+    static_assert(std::is_same_v<A, std::conditional_t<PARAMS || SCORED, CvScoreArgs, CvRecArgs>>, "argument block");
     constexpr int N = 2 * D;
+    const CvRecArgs& ra = rec_args(ka);
     const CvArgs& a = ra.run;
     const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (f >= a.B) return;
@@ -70,6 +110,18 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
         vv[i] = ldb<T>(a.P, tri<N>(D + i, D + i), rb, off);
         r[i] = T(a.r[tri<D>(i, i)]);
     }
+    double q_lane[2] = {0.0, 0.0};  // PARAMS: the lane's q_pos, q_vel
+    if constexpr (PARAMS) {
+        q_lane[0] = a.q_pos;
+        q_lane[1] = a.q_vel;
+        if (ka.consts != nullptr) {  // wave-uniform
+            const uint32_t off8 = uint32_t(f) * 8u, rb8 = uint32_t(a.B) * 8u;
+            q_lane[0] = ldb<double>(ka.consts, 0, rb8, off8);
+            q_lane[1] = ldb<double>(ka.consts, 1, rb8, off8);
+#pragma unroll
+            for (int i = 0; i < D; ++i) r[i] = T(ldb<double>(ka.consts, 2 + i, rb8, off8));
+        }
+    }
     int32_t st = a.status[f];
     const int T_ = a.T;
     const int k_upd = a.update_every;
@@ -83,8 +135,25 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
     const uint32_t rb_m = (has_mask && U > 0) ? uint32_t(a.B) : 0u;  // mask rows are [B] bytes
     const T dt0 = T(a.dt);
     const T hdt20 = T(0.5) * dt0 * dt0;
-    const T qp0 = T(a.q_pos * a.dt), qv0 = T(a.q_vel * a.dt);
-    auto load_in = [&](int t, RecIn<D, T>& in) {
+    // (the handle's constants stay read from the argument block in their own expressions: routing
+    // them through a local changed the existing instantiations' instruction streams)
+    T qp0, qv0;
+    if constexpr (PARAMS) {
+        qp0 = T(q_lane[0] * a.dt);
+        qv0 = T(q_lane[1] * a.dt);
+    } else {
+        qp0 = T(a.q_pos * a.dt);
+        qv0 = T(a.q_vel * a.dt);
+    }
+    using In = std::conditional_t<SCORED, RecInScored<D, T>, RecIn<D, T>>;
+    std::conditional_t<SCORED, CvScoreAcc, NoCvScore> sc;
+    bool has_track = false;
+    uint32_t rb_tk = 0u;
+    if constexpr (SCORED) {
+        has_track = ka.track != nullptr;
+        rb_tk = has_track ? rb : 0u;
+    }
+    auto load_in = [&](int t, In& in) {
         const int tc = t < T_ ? t : T_ - 1;
         if (tc > ld_upd_step) {
             ld_upd_step += k_upd;
@@ -100,9 +169,13 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
         for (int i = 0; i < D; ++i) in.z[i] = ldb_stream(a.z, int64_t(s) * D + i, rbz, off, T(0));
         // a zero-length row (no mask, or no update at this step) loads 0: no branch, no address
         in.use = GENERAL ? ldb<uint8_t>(a.mask, s, upd ? rb_m : 0u, uint32_t(f)) : uint8_t(1);
+        if constexpr (SCORED) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) in.tr[i] = ldb_stream(ka.track, int64_t(tc) * D + i, rb_tk, off, T(0));
+        }
     };
     int until_upd = k_upd;
-    auto step = [&](int t, const RecIn<D, T>& in) {
+    auto step = [&](int t, const In& in) {
         // GENERAL: cv_run_kernel's per-step dt in its own expressions, statement for statement.  The
         // shape matters, not only the values: with Q dt formed in the step, next to the sum it
         // enters, the compiler contracts q dt + P into one fma in fp64 there and here alike
@@ -113,8 +186,13 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
             const double dtd = has_dts ? a.dt_steps[t] : a.dt;
             dt = T(dtd);
             hdt2 = T(0.5) * dt * dt;
-            qp = T(a.q_pos * dtd);
-            qv = T(a.q_vel * dtd);
+            if constexpr (PARAMS) {
+                qp = T(q_lane[0] * dtd);
+                qv = T(q_lane[1] * dtd);
+            } else {
+                qp = T(a.q_pos * dtd);
+                qv = T(a.q_vel * dtd);
+            }
         }
         // predict (Cv::predict per axis): Bm' = Bm + dt C, A' = A + dt (Bm' + Bm^T), + Q
 #pragma unroll
@@ -141,6 +219,12 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
                 const T dinv = rcp_pos<2>(S);
                 const T k0 = pp[i] * dinv, k1 = pv[i] * dinv;
                 const T y = in.z[i] - xp[i];
+                if constexpr (SCORED) {
+                    // the update's own y, S and reciprocal; a masked lane adds 0 and multiplies by 1
+                    const T term = (y * y) * dinv;
+                    sc.nis += app ? double(term) : 0.0;
+                    sc.ldm *= app ? double(S) : 1.0;
+                }
                 const T nxp = fmaT(k0, y, xp[i]);
                 const T nxv = fmaT(k1, y, xv[i]);
                 const T e0 = fmaT(k0, S, -pp[i]);
@@ -165,6 +249,23 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
                 vv[i] = app ? vv[i] + poison : vv[i];
             }
             st = (ok || !app) ? st : kNotSpd;
+            if constexpr (SCORED) {
+                renorm(sc.ldm, sc.lde);
+                sc.ngps += app ? 1 : 0;
+            }
+        }
+        if constexpr (SCORED) {
+            // the position after the step against the track row, both as doubles
+            bool have = has_track;
+            double e2 = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                have = have && (in.tr[i] == in.tr[i]);
+                const double e = double(xp[i]) - double(in.tr[i]);
+                e2 = fmaT(e, e, e2);
+            }
+            sc.sse += have ? e2 : 0.0;
+            sc.npos += have ? 1 : 0;
         }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -206,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
         }
     };
     // cv_block_kernel's input ring: DEPTH statically named buffers, prologue drained once
-    RecIn<D, T> buf[DEPTH];
+    In buf[DEPTH];
 #pragma unroll
     for (int j = 0; j < DEPTH - 1; ++j) load_in(j, buf[j]);
     __builtin_amdgcn_s_waitcnt(0);
@@ -230,6 +331,21 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
         stb(a.P, tri<N>(D + i, D + i), rb, off, vv[i]);
     }
     a.status[f] = st;
+    if constexpr (SCORED) {
+        // rows KF_SCORE_*: the IMU rows are 0; a filter that is not KF_OK keeps its counts only
+        const uint32_t off8 = uint32_t(f) * 8u;
+        const uint32_t rb8 = ka.scores != nullptr ? uint32_t(a.B) * 8u : 0u;
+        const bool good = st == 0;
+        const double nanv = quiet_nan<double>();
+        stb(ka.scores, kScoreGpsN, rb8, off8, double(sc.ngps));
+        stb(ka.scores, kScoreGpsNis, rb8, off8, good ? sc.nis : nanv);
+        stb(ka.scores, kScoreGpsLogdetS, rb8, off8, good ? log_mant(sc.ldm, sc.lde) : nanv);
+        stb(ka.scores, kScoreImuN, rb8, off8, 0.0);
+        stb(ka.scores, kScoreImuNis, rb8, off8, 0.0);
+        stb(ka.scores, kScoreImuLogdetS, rb8, off8, 0.0);
+        stb(ka.scores, kScorePosN, rb8, off8, double(sc.npos));
+        stb(ka.scores, kScorePosSse, rb8, off8, good ? sc.sse : nanv);
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -252,6 +368,10 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const CvRecArgs ra) {
 // A NaN in a loaded row (state, covariance or control) or a non-positive pivot of P_p poisons the
 // filter from that t down to 0: NaN rows, KF_ENOTSPD in sm_status; the rows above are stored.
 // sm_logdet takes the LDL pivots of P_s in the forward log-det's order and form.
+// PARAMS (kf_smooth_run_params; the argument block is then CvSmoothParamArgs, A): q_pos and q_vel
+// are the lane's column of ka.consts (rows 0 and 1 of kf_run_scores' table), loaded once, and enter
+// the expressions the handle's own enter; a NULL table selects the handle's.  Without PARAMS the
+// kernel is instruction for instruction what it was.
 // ------------------------------------------------------------------------------------
 #ifndef KF_CV_SMOOTH_DEPTH
 #define KF_CV_SMOOTH_DEPTH 4
@@ -265,14 +385,26 @@ struct SmoothRow {
     double u[D];
 };
 
-template <int D, int DEPTH>
-__global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const CvSmoothArgs a) {
+__device__ __forceinline__ const CvSmoothArgs& smooth_args(const CvSmoothArgs& a) { return a; }
+__device__ __forceinline__ const CvSmoothArgs& smooth_args(const CvSmoothParamArgs& a) { return a.smooth; }
+
+template <int D, int DEPTH, bool PARAMS = false, typename A = CvSmoothArgs>
+__global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
+    static_assert(std::is_same_v<A, std::conditional_t<PARAMS, CvSmoothParamArgs, CvSmoothArgs>>, "argument block");
     using T = double;
     constexpr int N = 2 * D, NP = 3 * D;
+    const CvSmoothArgs& a = smooth_args(ka);
     const int64_t f = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (f >= a.B) return;
     const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
     const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
+    double q_pos = a.q_pos, q_vel = a.q_vel;
+    if constexpr (PARAMS) {
+        if (ka.consts != nullptr) {  // wave-uniform
+            q_pos = ldb<double>(ka.consts, 0, rb, off);
+            q_vel = ldb<double>(ka.consts, 1, rb, off);
+        }
+    }
     const bool has_dts = a.dt_steps != nullptr;
     const bool need_ld = a.sm_logdet != nullptr;
     const uint32_t rb_u = a.u != nullptr ? rb : 0u;      // no control: loads return 0
@@ -359,7 +491,7 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const CvSmoothArgs a)
     if (n > 0) {
         T dt = T(a.dt);
         T hdt2 = T(0.5) * dt * dt;
-        T qp = T(a.q_pos * a.dt), qv = T(a.q_vel * a.dt);
+        T qp = T(q_pos * a.dt), qv = T(q_vel * a.dt);
         auto load = [&](int s, SmoothRow<D>& in) {
             const int t = T_ - 2 - (s < n ? s : n - 1);
             load_xP(t, in.x, in.P);
@@ -372,8 +504,8 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const CvSmoothArgs a)
                 const double dtd = a.dt_steps[t + 1];
                 dt = T(dtd);
                 hdt2 = T(0.5) * dt * dt;
-                qp = T(a.q_pos * dtd);
-                qv = T(a.q_vel * dtd);
+                qp = T(q_pos * dtd);
+                qv = T(q_vel * dtd);
             }
             bool bad = false;
 #pragma unroll
@@ -453,6 +585,21 @@ void launch_rec_t(const CvRecArgs& a, dim3 grid, hipStream_t st) {
     else cv_rec_kernel<D, T, 8, false, true><<<grid, kBlock, 0, st>>>(a);
 }
 
+// kf_run_scores' instantiations: PARAMS and SCORED both on and every record optional, one per
+// input shape; a NULL consts, track or scores is a wave-uniform select or a zero-length row
+#ifndef KF_CV_SCORES_DEPTH
+#define KF_CV_SCORES_DEPTH 4
+#endif
+constexpr int kCvScoresDepth = KF_CV_SCORES_DEPTH;  // their input ring (the depth changes no bit)
+
+template <int D, typename T>
+void launch_scores_t(const CvScoreArgs& a, dim3 grid, hipStream_t st) {
+    const CvArgs& r = a.rec.run;
+    const bool general = r.dt_steps != nullptr || r.u == nullptr || r.mask != nullptr;  // as launch_rec_t
+    if (general) cv_rec_kernel<D, T, kCvScoresDepth, true, true, true, true, CvScoreArgs><<<grid, kBlock, 0, st>>>(a);
+    else cv_rec_kernel<D, T, kCvScoresDepth, false, true, true, true, CvScoreArgs><<<grid, kBlock, 0, st>>>(a);
+}
+
 }  // namespace
 
 hipError_t launch_cv_rec(int axes, bool f64, const CvRecArgs& a, hipStream_t stream) {
@@ -465,6 +612,29 @@ hipError_t launch_cv_rec(int axes, bool f64, const CvRecArgs& a, hipStream_t str
         if (f64) launch_rec_t<3, double>(a, grid, stream);
         else launch_rec_t<3, float>(a, grid, stream);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_cv_scores(int axes, bool f64, const CvScoreArgs& a, hipStream_t stream) {
+    const CvArgs& r = a.rec.run;
+    if (r.B <= 0 || r.T <= 0 || (axes != 2 && axes != 3)) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((r.B + kBlock - 1) / kBlock));
+    if (axes == 2) {
+        if (f64) launch_scores_t<2, double>(a, grid, stream);
+        else launch_scores_t<2, float>(a, grid, stream);
+    } else {
+        if (f64) launch_scores_t<3, double>(a, grid, stream);
+        else launch_scores_t<3, float>(a, grid, stream);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cv_smooth_params(int axes, const CvSmoothParamArgs& p, hipStream_t stream) {
+    const CvSmoothArgs& a = p.smooth;
+    if (a.B <= 0 || a.T <= 0 || (axes != 2 && axes != 3) || !a.filt_x || !a.filt_P) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+    if (axes == 2) cv_smooth_kernel<2, kCvSmoothDepth, true, CvSmoothParamArgs><<<grid, kBlock, 0, stream>>>(p);
+    else cv_smooth_kernel<3, kCvSmoothDepth, true, CvSmoothParamArgs><<<grid, kBlock, 0, stream>>>(p);
     return hipGetLastError();
 }
 

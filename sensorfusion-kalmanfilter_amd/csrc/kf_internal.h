@@ -56,6 +56,21 @@ struct CvSmoothArgs {
     double q_pos, q_vel;     // Q = diag(q_pos dt, q_vel dt)
 };
 
+// kf_run_scores (cv_rec_kernel's PARAMS / SCORED instantiations): kf_run_rec's block, untouched, and
+// what the two additions read and write.  Each of the three may be nullptr.
+struct CvScoreArgs {
+    CvRecArgs rec;
+    const double* consts;    // [2 + axes][B]: q_pos, q_vel, then the diagonal of R (kf.h's KF_CV_CONST_*)
+    const void* track;       // [T][axes][B] in the handle's dtype
+    double* scores;          // [kScoreRows][B]
+};
+
+// kf_smooth_run_params (cv_smooth_kernel's PARAMS instantiations): the Q rows of the same table
+struct CvSmoothParamArgs {
+    CvSmoothArgs smooth;
+    const double* consts;    // [2 + axes][B] or nullptr: smooth.q_pos / q_vel
+};
+
 struct SynthArgs {
     int64_t B;
     int64_t filter_offset;
@@ -539,6 +554,10 @@ hipError_t launch_synth(int axes, bool f64, const SynthArgs& a, hipStream_t stre
 // caller has checked both), and the RTS backward pass over such a record (f64 only)
 hipError_t launch_cv_rec(int axes, bool f64, const CvRecArgs& a, hipStream_t stream);
 hipError_t launch_cv_smooth(int axes, const CvSmoothArgs& a, hipStream_t stream);
+// the same two under per-filter constants, the forward run scored in the launch (kf_run_scores,
+// kf_smooth_run_params)
+hipError_t launch_cv_scores(int axes, bool f64, const CvScoreArgs& a, hipStream_t stream);
+hipError_t launch_cv_smooth_params(int axes, const CvSmoothParamArgs& a, hipStream_t stream);
 // bytes (a multiple of 4) from src to dst on the stream, by a kernel
 hipError_t launch_copy(void* dst, const void* src, size_t bytes, hipStream_t stream);
 // chain = true: the chain-parallel kernel (kGroup lanes per filter), for few filters.

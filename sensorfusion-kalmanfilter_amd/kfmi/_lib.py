@@ -46,6 +46,14 @@ KF_SCORE_IMU_LOGDET_S = 5
 KF_SCORE_POS_N = 6
 KF_SCORE_POS_SSE = 7
 KF_SCORE_ROWS = 8
+KF_CV_CONST_Q_POS = 0
+KF_CV_CONST_Q_VEL = 1
+KF_CV_CONST_R = 2
+
+
+def KF_CV_CONST_ROWS(d):
+    return 2 + d
+
 
 KF_OPT_PREDICT = 1
 KF_OPT_CV_KERNEL = 2
@@ -121,6 +129,8 @@ SIGNATURES = {
     'kf_run': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_run_rec': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'kf_smooth_run': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kf_run_scores': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kf_smooth_run_params': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kf_synth': (_i, [_vp, ctypes.c_uint64, _i64, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'kf_run_events': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),
     'kf_run_events_seq': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),

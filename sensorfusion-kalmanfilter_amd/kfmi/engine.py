@@ -94,16 +94,44 @@ SweepScores = collections.namedtuple('SweepScores', 'scores n_updated traj logde
 SmoothedSweep = collections.namedtuple('SmoothedSweep', 'x P traj logdet status')
 SmoothedRun = collections.namedtuple('SmoothedRun', 'x P logdet status')
 RunSmoothed = collections.namedtuple('RunSmoothed', 'traj cov logdet smoothed')
+ScoredRun = collections.namedtuple('ScoredRun', 'scores traj cov logdet')
+
+
+def cv_consts_table(model, sets):
+    """The [2 + d, B] float64 table of B constant sets for a 'cv2' / 'cv3' handle (run_scores,
+    smooth_run's ``consts``): column f is sets[f] = (q_pos, q_vel, r) or a dict with those keys, r
+    the d diagonal entries of R (a scalar: the same on every axis).  P0 is not part of it."""
+    if model not in ('cv2', 'cv3'):
+        raise KFError(_lib.KF_EINVAL, f'cv_consts_table: model {model!r} is not cv2 / cv3')
+    d = MODELS[model][2]
+    tab = np.empty((_lib.KF_CV_CONST_ROWS(d), len(sets)), np.float64)
+    for f, c in enumerate(sets):
+        try:
+            q_pos, q_vel, r = (c['q_pos'], c['q_vel'], c['r']) if isinstance(c, dict) else c
+            r = np.broadcast_to(np.asarray(r, np.float64), (d,)) if np.ndim(r) == 0 else np.asarray(r, np.float64)
+            q_pos, q_vel = float(q_pos), float(q_vel)
+        except (KeyError, TypeError, ValueError) as e:
+            raise KFError(_lib.KF_EINVAL, f'cv_consts_table: set {f}: (q_pos, q_vel, r[{d}]) expected: {e}') from e
+        if r.shape != (d,):
+            raise KFError(_lib.KF_EINVAL, f'cv_consts_table: set {f}: r has shape {r.shape}, expected ({d},)')
+        tab[_lib.KF_CV_CONST_Q_POS, f] = q_pos
+        tab[_lib.KF_CV_CONST_Q_VEL, f] = q_vel
+        tab[_lib.KF_CV_CONST_R:, f] = r
+    return tab
 
 
 def innovation_nll(scores, model, sensor):
     """The Gaussian innovation negative log-likelihood per filter from run_sweep_scores' table
     ([8, B], a tensor or an array): -sum over the sensor's applied updates of log N(y; 0, S) =
     0.5 (NIS + logdet_S + n m log 2 pi), m the measurement's length (GPS 3 | 2, IMU 15 | 8 for
-    'ref15' | 'ref8').  ``sensor``: 'gps' | 'imu'."""
-    if model not in REF_MODELS or sensor not in ('gps', 'imu'):
+    'ref15' | 'ref8').  ``sensor``: 'gps' | 'imu'.  run_scores' table of a 'cv2' / 'cv3' handle:
+    'gps' only, m = d."""
+    if model in ('cv2', 'cv3') and sensor == 'gps':
+        m = MODELS[model][2]
+    elif model not in REF_MODELS or sensor not in ('gps', 'imu'):
         raise ValueError(f'innovation_nll: model {model!r}, sensor {sensor!r}')
-    m = {'ref15': (3, 15), 'ref8': (2, 8)}[model][sensor == 'imu']
+    else:
+        m = {'ref15': (3, 15), 'ref8': (2, 8)}[model][sensor == 'imu']
     n, nis, ld = (scores[SCORE_ROWS[f'{sensor}_{k}']] for k in ('n', 'nis', 'logdet_s'))
     return 0.5 * (nis + ld + n * (m * math.log(2.0 * math.pi)))
 
@@ -374,8 +402,47 @@ class BatchedKF:
                                     int(update_every), _ptr(tr), _ptr(cv), _ptr(ld), self._stream()))
         return tr, cv, ld
 
+    def run_scores(self, u, z, consts=None, track=None, dt=None, dt_steps=None, update_every=1, mask=None,
+                   scores=True, traj=False, cov=False, logdet=False):
+        """``run_rec`` under per-filter constants, scored in the launch (kf_run_scores).  consts
+        [2 + d, B] float64 (``cv_consts_table``) or None = the handle's; track [T, d, B] in the
+        handle's dtype (NaN rows are not scored) or None; the other arguments as in ``run_rec``.
+        Returns ScoredRun(scores [8, B] float64 in SCORE_ROWS' layout, traj, cov, logdet), None
+        where not asked for.  ``innovation_nll(scores, model, 'gps')`` gives the likelihood."""
+        self._need_cv('run_scores')
+        if u is not None:
+            T = int(u.shape[0])
+        elif dt_steps is not None:
+            T = int(dt_steps.shape[0])
+        else:
+            T = int(z.shape[0]) * int(update_every)
+        U = T // update_every
+        ud = self._dev(u, (T, self.c, self.batch), 'u') if u is not None else None
+        zd = self._dev(z, (U, self.m, self.batch), 'z') if U > 0 else None
+        md = self._dev(mask, (U, self.batch), 'mask', torch.uint8) if mask is not None else None
+        dts = self._dev(dt_steps, (T,), 'dt_steps', torch.float64) if dt_steps is not None else None
+        if dts is None and dt is None:
+            raise ValueError('run_scores: give dt (scalar) or dt_steps [T]')
+        cd = self._cv_consts(consts)
+        tk = self._dev(track, (T, self.c, self.batch), 'track') if track is not None else None
+        if tk is not None and not scores:
+            raise KFError(_lib.KF_EINVAL, 'run_scores: a track needs scores=True')
+        sc = torch.empty(_lib.KF_SCORE_ROWS, self.batch, dtype=torch.float64, device=self.device) if scores else None
+        tr = self.empty(T, self.n, self.batch) if traj else None
+        cv = self.empty(T, 3 * self.c, self.batch) if cov else None
+        ld = self.empty(T, self.batch) if logdet else None
+        check(_lib.lib().kf_run_scores(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(zd), _ptr(md),
+                                       int(update_every), _ptr(cd), _ptr(tk), _ptr(sc), _ptr(tr), _ptr(cv), _ptr(ld),
+                                       self._stream()))
+        return ScoredRun(sc, tr, cv, ld)
+
+    def _cv_consts(self, consts):
+        if consts is None:
+            return None
+        return self._dev(consts, (_lib.KF_CV_CONST_ROWS(self.c), self.batch), 'consts', torch.float64)
+
     def smooth_run(self, filt_x, filt_P, u=None, dt=None, dt_steps=None, x=True, P=False, logdet=False, status=True,
-                   inplace=False):
+                   inplace=False, consts=None):
         """The RTS smoother over a ``run_rec`` record (kf_smooth_run): filt_x [T, n, B] its traj,
         filt_P [T, 3 d, B] its cov (device tensors or arrays); u, dt / dt_steps the forward run's
         (u None: zero control).  An f64 cv2 / cv3 handle, whose state and status are not touched.
@@ -383,7 +450,8 @@ class BatchedKF:
         not asked for; row T - 1 is the filtered row.  ``inplace``: x and P (where asked for)
         overwrite filt_x / filt_P, which must then be contiguous device tensors.  A filter whose
         record is not positive definite (or holds a NaN) has NaN rows from there down to 0 and
-        KF_ENOTSPD in ``status``."""
+        KF_ENOTSPD in ``status``.  consts [2 + d, B] (``cv_consts_table``): filter f smooths under
+        column f's q_pos / q_vel (kf_smooth_run_params), as ``run_scores`` filtered it."""
         self._need_cv('smooth_run')
         if self.dtype != 'f64':
             raise KFError(_lib.KF_EINVAL, 'smooth_run: needs an f64 handle')
@@ -402,17 +470,29 @@ class BatchedKF:
         sP = (fP if inplace else self.empty(T, 3 * self.c, self.batch)) if P else None
         ld = self.empty(T, self.batch) if logdet else None
         st = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if status else None
-        check(_lib.lib().kf_smooth_run(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(fx), _ptr(fP),
-                                       _ptr(sx), _ptr(sP), _ptr(ld), _ptr(st), self._stream()))
+        if consts is not None:
+            check(_lib.lib().kf_smooth_run_params(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(fx),
+                                                  _ptr(fP), _ptr(sx), _ptr(sP), _ptr(ld), _ptr(st),
+                                                  _ptr(self._cv_consts(consts)), self._stream()))
+        else:
+            check(_lib.lib().kf_smooth_run(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(fx), _ptr(fP),
+                                           _ptr(sx), _ptr(sP), _ptr(ld), _ptr(st), self._stream()))
         return SmoothedRun(sx, sP, ld, st)
 
     def run_smoothed(self, u, z, dt=None, dt_steps=None, update_every=1, mask=None, logdet=True, P=False,
-                     smoothed_logdet=False):
+                     smoothed_logdet=False, consts=None):
         """``run_rec`` then ``smooth_run`` out of place: RunSmoothed(traj, cov, logdet, smoothed), the
         filtered track, covariance record and log det, and ``smoothed`` = SmoothedRun(x, P, logdet,
-        status).  An f64 cv2 / cv3 handle."""
+        status).  An f64 cv2 / cv3 handle.  consts [2 + d, B]: both halves under per-filter
+        constants (``run_scores`` without scores, then ``smooth_run(consts=...)``)."""
         if self.dtype != 'f64':
             raise KFError(_lib.KF_EINVAL, 'run_smoothed: needs an f64 handle')
+        if consts is not None:
+            cd = self._cv_consts(consts)
+            _, tr, cv, ld = self.run_scores(u, z, consts=cd, dt=dt, dt_steps=dt_steps, update_every=update_every,
+                                            mask=mask, scores=False, traj=True, cov=True, logdet=logdet)
+            sm = self.smooth_run(tr, cv, u=u, dt=dt, dt_steps=dt_steps, P=P, logdet=smoothed_logdet, consts=cd)
+            return RunSmoothed(tr, cv, ld, sm)
         tr, cv, ld = self.run_rec(u, z, dt=dt, dt_steps=dt_steps, update_every=update_every, mask=mask,
                                   logdet=logdet)
         sm = self.smooth_run(tr, cv, u=u, dt=dt, dt_steps=dt_steps, P=P, logdet=smoothed_logdet)
