@@ -431,6 +431,62 @@ int kf_smooth_run_params(kf_batch* handle, int T, double dt, const double* dt_st
                          void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status,
                          const double* consts, void* stream);
 
+/* Rows of kf_smooth_run_em's statistics table: device [KF_EM_ROWS(d)][B] double, filter index
+ * fastest, d = 2 | 3 axes. */
+#define KF_EM_N_TRANS   0   /* transitions counted                                            */
+#define KF_EM_Q_POS     1   /* sum over them of sum_axis E[w_pos^2 | all data] / dt_t         */
+#define KF_EM_Q_VEL     2   /* ... E[w_vel^2 | all data] / dt_t                               */
+#define KF_EM_N_FIX     3   /* applied fixes                                                  */
+#define KF_EM_R         4   /* + axis: sum over them of (z - p_s)^2 + P_s[pp]                 */
+#define KF_EM_ROWS(d)   (4 + (d))
+
+/* kf_smooth_run_params that also gathers, per filter, the sufficient statistics of one EM
+ * iteration for q_pos, q_vel and the diagonal of R (the smoothed moments are EM's E-step), and
+ * optionally smooths the state the forward run started from.  f64 KF_MODEL_CV2 / KF_MODEL_CV3
+ * handles.  Every argument it shares with kf_smooth_run_params means what it means there (dt /
+ * dt_steps, NULL u, the record and output layouts, running in place, failure per filter, consts
+ * NULL = the handle's q, T = 1, its KF_EINVAL cases), and sm_x, sm_P, sm_logdet and sm_status are
+ * bit for bit kf_smooth_run_params' on the same inputs.  The handle's state, its status and a
+ * held-back kf_predict are neither read nor touched.
+ *
+ * z, mask, update_every: kf_run's, those of the forward run that wrote the record.  z NULL leaves
+ * KF_EM_N_FIX and the R rows at 0.
+ * init_x [n][B], init_P [3 d][B] (block-packed like a record row), both given or both NULL: the
+ * state the forward run started from.  Given, one more backward step takes it as the filtered row
+ * before step 0, with dt[0] and u[0], writes its smoothed row to sm_init_x [n][B] / sm_init_P
+ * [3 d][B] (each may be NULL; exactly init_x / init_P is legal) and counts the transition into step
+ * 0; a failure there is reported in sm_status like any other.  NULL: T - 1 transitions.
+ *
+ * em, device [KF_EM_ROWS(d)][B] double, overwritten, may be NULL:
+ *   The transition into step t has the noise w_t = x_t - F x_{t-1} - G u_t over d = dt[t].  With
+ *   J = Q d P_p^-1, E[w | all data] = J (x_s[t] - x_p) and Var[w | all data] = Q d + J (P_s[t] - P_p)
+ *   J^T, from the LDL^T of P_p and the differences the smoothing step forms anyway (the textbook
+ *   lag-one form e e^T + P_s[t] + F P_s[t-1] F^T - F L - L^T F^T, L = C_{t-1} P_s[t], is the same
+ *   quantity).  KF_EM_Q_POS / KF_EM_Q_VEL: the sum over the counted transitions of the two diagonal
+ *   entries of E[w] E[w]^T + Var[w], each over d, axes added in order.  A transition with d == 0
+ *   adds nothing and is not counted.
+ *   KF_EM_R + i: the sum over the fixes the forward run applied (step t with (t + 1) %
+ *   update_every == 0 whose mask entry is non-zero, or mask NULL) of (z_i - p_s,i)^2 + P_s[pp]_i of
+ *   the smoothed row t.
+ *   The M-step is q_pos = Q_POS / (d N_TRANS), q_vel = Q_VEL / (d N_TRANS), r_i = R_i / N_FIX
+ *   (kfmi.cv_em_update).  The counts depend only on T, update_every, mask, dt and whether init_* is
+ *   given; a filter whose sm_status is not 0 has NaN in its float rows and keeps its counts.  T = 0
+ *   zeroes the table.
+ *
+ * Bit for bit: everything is lane-local and summed in double in backward step order, so a filter's
+ * rows are the same on every run and do not depend on B, on its place in its wave, on which sm_*
+ * outputs are NULL or on running in place.  Asynchronous on `stream`, capturable; no workspace, no
+ * atomics.  KF_EINVAL before anything is queued, besides kf_smooth_run_params' cases:
+ * update_every < 1, mask given with z NULL, one of init_x / init_P without the other, sm_init_x or
+ * sm_init_P without init_*.  Not built: the reference models' sweep (kf_smooth_sweep), f32, a full
+ * Q or R, estimates of x0 / P0.  The reference estimates no noise constants. */
+int kf_smooth_run_em(kf_batch* handle, int T, double dt, const double* dt_steps, const void* u,
+                     const void* z, const uint8_t* mask, int update_every,
+                     const void* filt_x, const void* filt_P, const void* init_x, const void* init_P,
+                     void* sm_x, void* sm_P, void* sm_logdet, int32_t* sm_status,
+                     void* sm_init_x, void* sm_init_P,
+                     const double* consts, double* em, void* stream);
+
 /* Deterministic synthetic GPS+IMU streams for filters
  * [filter_offset, filter_offset + B) of a global population: counter-based Philox4x32-10
  * keyed by seed and the GLOBAL filter index, so any shard regenerates its own slice.

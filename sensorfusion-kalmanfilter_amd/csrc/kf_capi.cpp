@@ -915,18 +915,33 @@ int kf_run_scores(kf_batch* h, int T, double dt, const double* dt_steps, const v
 
 namespace {
 
-// kf_smooth_run and kf_smooth_run_params (fn names the caller): consts = nullptr is kf_smooth_run's
-// own launch
+// kf_smooth_run, kf_smooth_run_params and kf_smooth_run_em (fn names the caller): consts = nullptr
+// without em is kf_smooth_run's own launch; em: kf_smooth_run_em's further arguments (their block is
+// filled but for p, which this function builds)
 int smooth_run_impl(const char* fn, kf_batch* h, int T, double dt, const double* dt_steps, const void* u,
                     const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_logdet,
-                    int32_t* sm_status, const double* consts, void* stream) {
+                    int32_t* sm_status, const double* consts, void* stream, kfmi::CvSmoothEmArgs* em = nullptr) {
     if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
     if (is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_CV2 or KF_MODEL_CV3 handle (kf_smooth_sweep smooths "
                                           "the reference models)", fn);
     if (h->dtype != KF_F64) return fail(KF_EINVAL, "%s: needs an f64 handle (the f32 smoother is not built)", fn);
     if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
     if (!dt_steps && !(dt >= 0.0)) return fail(KF_EINVAL, "%s: dt must be >= 0 (got %g)", fn, dt);
-    if (T == 0 || h->B == 0) return KF_OK;
+    if (em) {
+        if (em->update_every < 1) return fail(KF_EINVAL, "%s: update_every = %d < 1", fn, em->update_every);
+        if (em->mask && !em->z) return fail(KF_EINVAL, "%s: a mask needs the z stream it masks", fn);
+        if (!em->init_x != !em->init_P)
+            return fail(KF_EINVAL, "%s: init_x and init_P are given together or not at all", fn);
+        if ((em->sm_init_x || em->sm_init_P) && !em->init_x)
+            return fail(KF_EINVAL, "%s: sm_init_x / sm_init_P need the initial row init_x / init_P", fn);
+    }
+    if (h->B == 0) return KF_OK;
+    if (T == 0) {
+        if (!em || !em->em) return KF_OK;
+        hipError_t e = hipMemsetAsync(em->em, 0, sizeof(double) * KF_EM_ROWS(h->axes) * static_cast<size_t>(h->B),
+                                      static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+    }
     if (!filt_x || !filt_P) return fail(KF_EINVAL, "%s: null filt_x/filt_P", fn);
     // every row is one [B] descriptor from a 64-bit base, as kf_run's streams: the only span limit
     // is the row's, B * 8 < 2 GiB, which kf_alloc has enforced; T has no limit of its own
@@ -945,7 +960,11 @@ int smooth_run_impl(const char* fn, kf_batch* h, int T, double dt, const double*
     a.q_pos = h->params.q_pos;
     a.q_vel = h->params.q_vel;
     hipError_t e;
-    if (!consts) {
+    if (em) {
+        em->p.smooth = a;
+        em->p.consts = consts;
+        e = kfmi::launch_cv_smooth_em(h->axes, *em, static_cast<hipStream_t>(stream));
+    } else if (!consts) {
         e = kfmi::launch_cv_smooth(h->axes, a, static_cast<hipStream_t>(stream));
     } else {
         kfmi::CvSmoothParamArgs pa{};
@@ -969,6 +988,24 @@ int kf_smooth_run_params(kf_batch* h, int T, double dt, const double* dt_steps, 
                          const double* consts, void* stream) {
     return smooth_run_impl("kf_smooth_run_params", h, T, dt, dt_steps, u, filt_x, filt_P, sm_x, sm_P, sm_logdet,
                            sm_status, consts, stream);
+}
+
+int kf_smooth_run_em(kf_batch* h, int T, double dt, const double* dt_steps, const void* u, const void* z,
+                     const uint8_t* mask, int update_every, const void* filt_x, const void* filt_P,
+                     const void* init_x, const void* init_P, void* sm_x, void* sm_P, void* sm_logdet,
+                     int32_t* sm_status, void* sm_init_x, void* sm_init_P, const double* consts, double* em,
+                     void* stream) {
+    kfmi::CvSmoothEmArgs ea{};
+    ea.z = z;
+    ea.mask = mask;
+    ea.update_every = update_every;
+    ea.init_x = init_x;
+    ea.init_P = init_P;
+    ea.sm_init_x = sm_init_x;
+    ea.sm_init_P = sm_init_P;
+    ea.em = em;
+    return smooth_run_impl("kf_smooth_run_em", h, T, dt, dt_steps, u, filt_x, filt_P, sm_x, sm_P, sm_logdet, sm_status,
+                           consts, stream, &ea);
 }
 
 int kf_synth(kf_batch* h, uint64_t seed, int64_t filter_offset, int T, double dt, int update_every,

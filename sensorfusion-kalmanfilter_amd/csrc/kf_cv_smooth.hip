@@ -3,7 +3,8 @@
 // filtered covariance (kf_run_rec), and cv_smooth_kernel, the Rauch-Tung-Striebel backward pass
 // over that record (kf_smooth_run).  Template flags of the same two kernels give every filter its
 // own q_pos, q_vel and R and score the run where it runs (kf_run_scores), and smooth under the same
-// per-filter Q (kf_smooth_run_params).
+// per-filter Q (kf_smooth_run_params); one more on the smoother adds the EM statistics for Q and R
+// and the smoothed row before step 0 (kf_smooth_run_em).
 //
 // Mapping, as in kf_cv.hip: ONE FILTER PER LANE, kBlock lanes per workgroup.  P is block-diagonal
 // over the axes, so a filter is D independent 2-state (pos_i, vel_i) chains: per axis x = (p, v)
@@ -372,6 +373,21 @@ __global__ __launch_bounds__(kBlock) void cv_rec_kernel(const A ka) {
 // are the lane's column of ka.consts (rows 0 and 1 of kf_run_scores' table), loaded once, and enter
 // the expressions the handle's own enter; a NULL table selects the handle's.  Without PARAMS the
 // kernel is instruction for instruction what it was.
+// EM (kf_smooth_run_em; PARAMS too, the argument block is then CvSmoothEmArgs): everything it adds
+// sits under `if constexpr`, and the instantiations without it are instruction for instruction
+// what they were (profiles/cv_em/isa_compare.log).  Three additions, all lane-local, summed in
+// double in backward step order, no atomics and no reduction:
+//   the row before step 0: with init_x / init_P one more backward step takes them as the filtered
+//   row before step 0 (d = dt[0], u[0]) and stores its smoothed row to sm_init_x / sm_init_P;
+//   the noise sums: the transition into step t + 1 has w = x[t + 1] - F x[t] - G u[t + 1], and with
+//   J = Q d P_p^-1 (the step's own LDL^T of P_p) E[w | all] = J (x_s[t + 1] - x_p) and
+//   Var[w | all] = Q d + J (P_s[t + 1] - P_p) J^T: the differences the smoothing step has already
+//   formed, nothing of P_s[t]; the two diagonal entries of E[w] E[w]^T + Var over d are added per
+//   axis, axes in order; a transition with d == 0 adds nothing and is not counted (wave-uniform);
+//   the R sums: the fix z[t / k] of a step the forward run updated at rides in the ring (zero-length
+//   rows elsewhere, as in cv_rec_kernel) with its mask byte, and after row t is smoothed axis i adds
+//   (z_i - p_s,i)^2 + P_s[pp]_i.
+// A filter whose status is not 0 has NaN in its float rows; its counts still count.
 // ------------------------------------------------------------------------------------
 #ifndef KF_CV_SMOOTH_DEPTH
 #define KF_CV_SMOOTH_DEPTH 4
@@ -384,13 +400,36 @@ struct SmoothRow {
     double P[3 * D];
     double u[D];
 };
+// EM: the step's fix rides in the ring with its other inputs
+template <int D>
+struct SmoothRowEm : SmoothRow<D> {
+    double z[D];
+    uint8_t use;
+};
+
+// EM: a lane's accumulators (kf_smooth_run_em)
+template <int D>
+struct CvEmAcc {
+    double qp = 0.0;    // sum over the counted transitions of sum_axis E[w_pos^2 | all] / d
+    double qv = 0.0;    // ... E[w_vel^2 | all] / d
+    double r[D] = {};   // per axis: sum over the applied fixes of (z - p_s)^2 + P_s[pp]
+    int32_t nfix = 0;   // applied fixes
+    int ntrans = 0;     // transitions counted (wave-uniform)
+};
+struct NoCvEm {};
 
 __device__ __forceinline__ const CvSmoothArgs& smooth_args(const CvSmoothArgs& a) { return a; }
 __device__ __forceinline__ const CvSmoothArgs& smooth_args(const CvSmoothParamArgs& a) { return a.smooth; }
+__device__ __forceinline__ const CvSmoothArgs& smooth_args(const CvSmoothEmArgs& a) { return a.p.smooth; }
+__device__ __forceinline__ const double* smooth_consts(const CvSmoothParamArgs& a) { return a.consts; }
+__device__ __forceinline__ const double* smooth_consts(const CvSmoothEmArgs& a) { return a.p.consts; }
 
-template <int D, int DEPTH, bool PARAMS = false, typename A = CvSmoothArgs>
+template <int D, int DEPTH, bool PARAMS = false, typename A = CvSmoothArgs, bool EM = false>
 __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
-    static_assert(std::is_same_v<A, std::conditional_t<PARAMS, CvSmoothParamArgs, CvSmoothArgs>>, "argument block");
+    static_assert(std::is_same_v<A, std::conditional_t<EM, CvSmoothEmArgs,
+                                                       std::conditional_t<PARAMS, CvSmoothParamArgs, CvSmoothArgs>>>,
+                  "argument block");
+    static_assert(PARAMS || !EM, "EM reads the constants' table as PARAMS does");
     using T = double;
     constexpr int N = 2 * D, NP = 3 * D;
     const CvSmoothArgs& a = smooth_args(ka);
@@ -400,9 +439,9 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
     const uint32_t rb = uint32_t(a.B) * uint32_t(sizeof(T));
     double q_pos = a.q_pos, q_vel = a.q_vel;
     if constexpr (PARAMS) {
-        if (ka.consts != nullptr) {  // wave-uniform
-            q_pos = ldb<double>(ka.consts, 0, rb, off);
-            q_vel = ldb<double>(ka.consts, 1, rb, off);
+        if (smooth_consts(ka) != nullptr) {  // wave-uniform
+            q_pos = ldb<double>(smooth_consts(ka), 0, rb, off);
+            q_vel = ldb<double>(smooth_consts(ka), 1, rb, off);
         }
     }
     const bool has_dts = a.dt_steps != nullptr;
@@ -465,10 +504,57 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
         for (int k = 0; k < NP; ++k) P[k] = ldb_stream(a.filt_P, int64_t(t) * NP + k, rb, off, T(0));
     };
 
+    // EM: the accumulators, and the fixes' rows counted down with the loads (rows are loaded in
+    // the order T - 1, T - 2, ...: ld_upd is the next update step at or below the row to load)
+    std::conditional_t<EM, CvEmAcc<D>, NoCvEm> em;
+    bool has_init = false, has_z = false, has_mask = false;
+    int k_upd = 1, ld_upd = -1, ld_zi = 0;
+    if constexpr (EM) {
+        has_init = ka.init_x != nullptr;
+        has_z = ka.z != nullptr;
+        has_mask = has_z && ka.mask != nullptr;
+        k_upd = ka.update_every;
+        ld_zi = T_ / k_upd - 1;
+        ld_upd = (ld_zi + 1) * k_upd - 1;
+    }
+    // the fix of row t and whether the lane applied it; live = false: a load past the last step
+    auto load_z = [&](int t, bool live, T (&z)[D], uint8_t& use) {
+        if constexpr (EM) {
+            const bool at = live && t >= 0 && t == ld_upd;  // wave-uniform
+            const bool upd = at && has_z;
+            const int zi = ld_zi > 0 ? ld_zi : 0;
+            const uint32_t rbz = upd ? rb : 0u;  // z only on update steps
+#pragma unroll
+            for (int i = 0; i < D; ++i) z[i] = ldb_stream(ka.z, int64_t(zi) * D + i, rbz, off, T(0));
+            // a zero-length row (no update at this row) loads 0
+            use = has_mask ? ldb<uint8_t>(ka.mask, zi, upd ? uint32_t(a.B) : 0u, uint32_t(f)) : uint8_t(upd);
+            if (at) {
+                ld_upd -= k_upd;
+                --ld_zi;
+            }
+        }
+    };
+    // the smoothed row against its fix
+    auto em_fix = [&](const T (&z)[D], uint8_t use) {
+        if constexpr (EM) {
+            const bool app = use != 0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                const T e = z[i] - sp[i];
+                const T term = fmaT(e, e, spp[i]);
+                em.r[i] += app ? term : T(0);
+            }
+            em.nfix += app ? 1 : 0;
+        }
+    };
+
     // row T - 1: the filtered row itself
     {
         T x[N], P[NP];
         load_xP(T_ - 1, x, P);
+        T z_last[D];
+        uint8_t use_last = 0;
+        if constexpr (EM) load_z(T_ - 1, true, z_last, use_last);
         __builtin_amdgcn_s_waitcnt(0);
         bool nan = false;
 #pragma unroll
@@ -485,20 +571,54 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
         }
         if (nan) poison();
         store_row(T_ - 1);
+        if constexpr (EM) em_fix(z_last, use_last);
     }
 
-    const int n = T_ - 1;  // backward steps; step s is row t = T - 2 - s (past the end: row 0 again)
+    // backward steps; step s is row t = T - 2 - s (past the end: row 0 again).  EM with the initial
+    // row: one more, t = -1, whose filtered row is (init_x, init_P)
+    const int n = EM ? T_ - 1 + (has_init ? 1 : 0) : T_ - 1;
     if (n > 0) {
         T dt = T(a.dt);
         T hdt2 = T(0.5) * dt * dt;
         T qp = T(q_pos * a.dt), qv = T(q_vel * a.dt);
-        auto load = [&](int s, SmoothRow<D>& in) {
+        using Row = std::conditional_t<EM, SmoothRowEm<D>, SmoothRow<D>>;
+        auto load = [&](int s, Row& in) {
             const int t = T_ - 2 - (s < n ? s : n - 1);
-            load_xP(t, in.x, in.P);
+            if constexpr (EM) {
+                // wave-uniform selects: the initial row is one record row of its own
+                const void* bx = t < 0 ? ka.init_x : a.filt_x;
+                const void* bP = t < 0 ? ka.init_P : a.filt_P;
+                const int tr = t < 0 ? 0 : t;
+#pragma unroll
+                for (int i = 0; i < N; ++i) in.x[i] = ldb_stream(bx, int64_t(tr) * N + i, rb, off, T(0));
+#pragma unroll
+                for (int k = 0; k < NP; ++k) in.P[k] = ldb_stream(bP, int64_t(tr) * NP + k, rb, off, T(0));
+                load_z(t, s < n, in.z, in.use);
+            } else {
+                load_xP(t, in.x, in.P);
+            }
 #pragma unroll
             for (int i = 0; i < D; ++i) in.u[i] = ldb_stream(a.u, int64_t(t + 1) * D + i, rb_u, off, T(0));
         };
-        auto step = [&](int s, const SmoothRow<D>& in) {
+        // EM: the smoothed row before step 0
+        auto store_init = [&]() {
+            if constexpr (EM) {
+                const uint32_t rb_ix = ka.sm_init_x != nullptr ? rb : 0u;  // absent outputs: stores dropped
+                const uint32_t rb_iP = ka.sm_init_P != nullptr ? rb : 0u;
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    stb_rec(ka.sm_init_x, i, rb_ix, off, sp[i]);
+                    stb_rec(ka.sm_init_x, D + i, rb_ix, off, sv[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    stb_rec(ka.sm_init_P, 3 * i, rb_iP, off, spp[i]);
+                    stb_rec(ka.sm_init_P, 3 * i + 1, rb_iP, off, spv[i]);
+                    stb_rec(ka.sm_init_P, 3 * i + 2, rb_iP, off, svv[i]);
+                }
+            }
+        };
+        auto step = [&](int s, const Row& in) {
             const int t = T_ - 2 - s;
             if (has_dts) {  // wave-uniform: the forward step t + 1's dt, in its expressions
                 const double dtd = a.dt_steps[t + 1];
@@ -506,6 +626,15 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
                 hdt2 = T(0.5) * dt * dt;
                 qp = T(q_pos * dtd);
                 qv = T(q_vel * dtd);
+            }
+            // EM: a transition of no duration carries no noise and is not counted (wave-uniform)
+            bool em_count = false;
+            T em_inv_d = T(0);
+            if constexpr (EM) {
+                const double d_em = has_dts ? a.dt_steps[t + 1] : a.dt;
+                em_count = d_em != 0.0;
+                em_inv_d = T(1) / T(d_em);
+                em.ntrans += em_count ? 1 : 0;
             }
             bool bad = false;
 #pragma unroll
@@ -545,6 +674,22 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
                 const T c10 = fmaT(-l10, c11, bn * i0);
                 const T dx0 = sp[i] - px, dx1 = sv[i] - pvx;
                 const T D00 = spp[i] - ppp, D01 = spv[i] - ppv, D11 = svv[i] - pvv;
+                if constexpr (EM) {
+                    if (em_count) {
+                        // J row r solves P_p j = (row r of Q d)^T, Q d = diag(qp, qv)
+                        const T j01 = (-l10 * qp) * i1;
+                        const T j00 = fmaT(-l10, j01, qp * i0);
+                        const T j11 = qv * i1;
+                        const T j10 = -l10 * j11;
+                        const T ew0 = fmaT(j01, dx1, j00 * dx0), ew1 = fmaT(j11, dx1, j10 * dx0);
+                        const T jd00 = fmaT(j01, D01, j00 * D00), jd01 = fmaT(j01, D11, j00 * D01);
+                        const T jd10 = fmaT(j11, D01, j10 * D00), jd11 = fmaT(j11, D11, j10 * D01);
+                        const T var0 = fmaT(jd01, j01, fmaT(jd00, j00, qp));
+                        const T var1 = fmaT(jd11, j11, fmaT(jd10, j10, qv));
+                        em.qp += fmaT(ew0, ew0, var0) * em_inv_d;
+                        em.qv += fmaT(ew1, ew1, var1) * em_inv_d;
+                    }
+                }
                 sp[i] = fmaT(c01, dx1, fmaT(c00, dx0, fx));
                 sv[i] = fmaT(c11, dx1, fmaT(c10, dx0, fv));
                 const T cd00 = fmaT(c01, D01, c00 * D00), cd01 = fmaT(c01, D11, c00 * D01);
@@ -554,9 +699,18 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
                 svv[i] = fmaT(cd11, c11, fmaT(cd10, c10, fvv));
             }
             if (bad || st != 0) poison();
-            store_row(t);
+            if constexpr (EM) {
+                if (t < 0) {  // wave-uniform
+                    store_init();
+                } else {
+                    store_row(t);
+                    em_fix(in.z, in.use);
+                }
+            } else {
+                store_row(t);
+            }
         };
-        SmoothRow<D> buf[DEPTH];
+        Row buf[DEPTH];
 #pragma unroll
         for (int j = 0; j < DEPTH - 1; ++j) load(j, buf[j]);
         __builtin_amdgcn_s_waitcnt(0);
@@ -573,6 +727,18 @@ __global__ __launch_bounds__(kBlock) void cv_smooth_kernel(const A ka) {
             if (s + j < n) step(s + j, buf[j]);
     }
     if (a.sm_status) a.sm_status[f] = st;
+    if constexpr (EM) {
+        // rows KF_EM_*: a filter that failed keeps its counts only
+        const uint32_t rb_em = ka.em != nullptr ? rb : 0u;
+        const bool good = st == 0;
+        const double nanv = quiet_nan<double>();
+        stb(ka.em, kEmNTrans, rb_em, off, double(em.ntrans));
+        stb(ka.em, kEmQPos, rb_em, off, good ? em.qp : nanv);
+        stb(ka.em, kEmQVel, rb_em, off, good ? em.qv : nanv);
+        stb(ka.em, kEmNFix, rb_em, off, double(em.nfix));
+#pragma unroll
+        for (int i = 0; i < D; ++i) stb(ka.em, kEmR + i, rb_em, off, good ? em.r[i] : nanv);
+    }
 }
 
 template <int D, typename T>
@@ -635,6 +801,25 @@ hipError_t launch_cv_smooth_params(int axes, const CvSmoothParamArgs& p, hipStre
     const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
     if (axes == 2) cv_smooth_kernel<2, kCvSmoothDepth, true, CvSmoothParamArgs><<<grid, kBlock, 0, stream>>>(p);
     else cv_smooth_kernel<3, kCvSmoothDepth, true, CvSmoothParamArgs><<<grid, kBlock, 0, stream>>>(p);
+    return hipGetLastError();
+}
+
+// kf_smooth_run_em's instantiations: their input ring holds D values of z and the mask byte more
+// per buffer and the lane 2 + D sums (the depth changes no bit).  At kf_smooth_run's depth of 4 the
+// three-axis kernel needs 318 registers, one wave per SIMD; at 2 it fits two, and measured 12.15 ms
+// against 12.41 with every output and 6.72 against 7.66 with the table alone (2^20 filters x 256
+// steps, profiles/cv_em/cv_em_timing_depth*.log)
+#ifndef KF_CV_EM_DEPTH
+#define KF_CV_EM_DEPTH 2
+#endif
+
+hipError_t launch_cv_smooth_em(int axes, const CvSmoothEmArgs& e, hipStream_t stream) {
+    const CvSmoothArgs& a = e.p.smooth;
+    if (a.B <= 0 || a.T <= 0 || (axes != 2 && axes != 3) || !a.filt_x || !a.filt_P || e.update_every < 1)
+        return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B + kBlock - 1) / kBlock));
+    if (axes == 2) cv_smooth_kernel<2, KF_CV_EM_DEPTH, true, CvSmoothEmArgs, true><<<grid, kBlock, 0, stream>>>(e);
+    else cv_smooth_kernel<3, KF_CV_EM_DEPTH, true, CvSmoothEmArgs, true><<<grid, kBlock, 0, stream>>>(e);
     return hipGetLastError();
 }
 

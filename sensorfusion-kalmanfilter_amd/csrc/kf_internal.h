@@ -71,6 +71,22 @@ struct CvSmoothParamArgs {
     const double* consts;    // [2 + axes][B] or nullptr: smooth.q_pos / q_vel
 };
 
+// kf_smooth_run_em (cv_smooth_kernel's EM instantiations): kf_smooth_run_params' block, untouched,
+// the forward run's fixes, the optional row before step 0 and the statistics table.  Rows of em
+// (kf.h's KF_EM_*): transitions counted, the two noise sums, fixes applied, then one R sum per axis.
+constexpr int kEmNTrans = 0, kEmQPos = 1, kEmQVel = 2, kEmNFix = 3, kEmR = 4;
+struct CvSmoothEmArgs {
+    CvSmoothParamArgs p;
+    const void* z;           // [T / update_every][axes][B] the forward run's fixes, or nullptr
+    const uint8_t* mask;     // [T / update_every][B] or nullptr
+    int update_every;
+    const void* init_x;      // [2 axes][B] the state the forward run started from, or nullptr
+    const void* init_P;      // [3 axes][B] block-packed like a record row; given with init_x
+    void* sm_init_x;         // [2 axes][B] or nullptr
+    void* sm_init_P;         // [3 axes][B] or nullptr
+    double* em;              // [4 + axes][B] or nullptr
+};
+
 struct SynthArgs {
     int64_t B;
     int64_t filter_offset;
@@ -558,6 +574,8 @@ hipError_t launch_cv_smooth(int axes, const CvSmoothArgs& a, hipStream_t stream)
 // kf_smooth_run_params)
 hipError_t launch_cv_scores(int axes, bool f64, const CvScoreArgs& a, hipStream_t stream);
 hipError_t launch_cv_smooth_params(int axes, const CvSmoothParamArgs& a, hipStream_t stream);
+// the backward pass with the EM statistics for Q and R and the row before step 0 (kf_smooth_run_em)
+hipError_t launch_cv_smooth_em(int axes, const CvSmoothEmArgs& a, hipStream_t stream);
 // bytes (a multiple of 4) from src to dst on the stream, by a kernel
 hipError_t launch_copy(void* dst, const void* src, size_t bytes, hipStream_t stream);
 // chain = true: the chain-parallel kernel (kGroup lanes per filter), for few filters.

@@ -55,6 +55,17 @@ def KF_CV_CONST_ROWS(d):
     return 2 + d
 
 
+KF_EM_N_TRANS = 0
+KF_EM_Q_POS = 1
+KF_EM_Q_VEL = 2
+KF_EM_N_FIX = 3
+KF_EM_R = 4
+
+
+def KF_EM_ROWS(d):
+    return 4 + d
+
+
 KF_OPT_PREDICT = 1
 KF_OPT_CV_KERNEL = 2
 KF_OPT_BLOCKS_PER_CU = 3
@@ -131,6 +142,8 @@ SIGNATURES = {
     'kf_smooth_run': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kf_run_scores': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kf_smooth_run_params': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kf_smooth_run_em': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp]),
     'kf_synth': (_i, [_vp, ctypes.c_uint64, _i64, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'kf_run_events': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),
     'kf_run_events_seq': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),

@@ -95,6 +95,12 @@ SmoothedSweep = collections.namedtuple('SmoothedSweep', 'x P traj logdet status'
 SmoothedRun = collections.namedtuple('SmoothedRun', 'x P logdet status')
 RunSmoothed = collections.namedtuple('RunSmoothed', 'traj cov logdet smoothed')
 ScoredRun = collections.namedtuple('ScoredRun', 'scores traj cov logdet')
+SmoothedEm = collections.namedtuple('SmoothedEm', 'x P logdet status init_x init_P em')
+NoiseFit = collections.namedtuple('NoiseFit', 'consts history nll status')
+
+# rows of smooth_run_em's [4 + d, B] table (kf.h's KF_EM_*; 'r' is the first of d rows)
+EM_ROWS = {'n_trans': _lib.KF_EM_N_TRANS, 'q_pos': _lib.KF_EM_Q_POS, 'q_vel': _lib.KF_EM_Q_VEL,
+           'n_fix': _lib.KF_EM_N_FIX, 'r': _lib.KF_EM_R}
 
 
 def cv_consts_table(model, sets):
@@ -118,6 +124,30 @@ def cv_consts_table(model, sets):
         tab[_lib.KF_CV_CONST_Q_VEL, f] = q_vel
         tab[_lib.KF_CV_CONST_R:, f] = r
     return tab
+
+
+def cv_em_update(em, consts, model):
+    """EM's M-step on smooth_run_em's statistics, per filter, in torch where the tables live: from
+    em [4 + d, B] and the table consts [2 + d, B] it was gathered under, the new table with
+    q_pos = Q_POS / (d N_TRANS), q_vel = Q_VEL / (d N_TRANS) and r_i = R_i / N_FIX.  A zero count
+    keeps the old value (no transition of a positive dt: both q; no applied fix: every r).  Tensors
+    (any device) or arrays; the result is of consts' kind.  A failed filter's NaN rows pass through."""
+    if model not in ('cv2', 'cv3'):
+        raise KFError(_lib.KF_EINVAL, f'cv_em_update: model {model!r} is not cv2 / cv3')
+    d = MODELS[model][2]
+    as_array = not torch.is_tensor(consts)
+    c = torch.as_tensor(consts, dtype=torch.float64)
+    e = torch.as_tensor(em, dtype=torch.float64).to(c.device)
+    rows_e, rows_c = _lib.KF_EM_ROWS(d), _lib.KF_CV_CONST_ROWS(d)
+    if e.ndim != 2 or c.ndim != 2 or e.shape[0] != rows_e or c.shape[0] != rows_c or e.shape[1] != c.shape[1]:
+        raise KFError(_lib.KF_EINVAL, f'cv_em_update: em {tuple(e.shape)} / consts {tuple(c.shape)}, expected '
+                                      f'({_lib.KF_EM_ROWS(d)}, B) / ({_lib.KF_CV_CONST_ROWS(d)}, B)')
+    n_tr, n_fix = e[_lib.KF_EM_N_TRANS], e[_lib.KF_EM_N_FIX]
+    out = torch.empty_like(c)
+    for row, src in ((_lib.KF_CV_CONST_Q_POS, _lib.KF_EM_Q_POS), (_lib.KF_CV_CONST_Q_VEL, _lib.KF_EM_Q_VEL)):
+        out[row] = torch.where(n_tr > 0, e[src] / (d * n_tr), c[row])
+    out[_lib.KF_CV_CONST_R:] = torch.where(n_fix > 0, e[_lib.KF_EM_R:] / n_fix, c[_lib.KF_CV_CONST_R:])
+    return out.numpy() if as_array else out
 
 
 def innovation_nll(scores, model, sensor):
@@ -497,6 +527,109 @@ class BatchedKF:
                                   logdet=logdet)
         sm = self.smooth_run(tr, cv, u=u, dt=dt, dt_steps=dt_steps, P=P, logdet=smoothed_logdet)
         return RunSmoothed(tr, cv, ld, sm)
+
+    def _block_rows(self):
+        """Rows of the tri-packed P [n (n + 1) / 2, B] that a covariance record row holds, in its order."""
+        n, d = self.n, self.c
+        tri = lambda i, j: i * n - i * (i - 1) // 2 + (j - i)  # noqa: E731
+        return [r for i in range(d) for r in (tri(i, i), tri(i, d + i), tri(d + i, d + i))]
+
+    def smooth_run_em(self, filt_x, filt_P, z, u=None, dt=None, dt_steps=None, update_every=1, mask=None, init=None,
+                      consts=None, x=False, P=False, logdet=False, status=True, inplace=False, init_out=True, em=True):
+        """``smooth_run`` that also gathers one EM iteration's statistics for q_pos, q_vel and R per
+        filter (kf_smooth_run_em).  filt_x, filt_P, u, dt / dt_steps, consts, x, P, logdet, status
+        and inplace as in ``smooth_run``; z [T // update_every, d, B] (or None: no R statistics),
+        mask and update_every the forward run's.  init = (x [n, B], P): the state the forward run
+        started from, P tri-packed [n (n + 1) / 2, B] as ``state()`` returns it (its same-axis rows are
+        gathered) or block-packed [3 d, B]; given, the transition into step 0 is counted and, with
+        init_out, the smoothed initial row returned.  Returns SmoothedEm(x, P, logdet, status,
+        init_x [n, B], init_P [3 d, B], em [4 + d, B] float64 in EM_ROWS' layout), None where not
+        asked for.  ``cv_em_update(em, consts, model)`` is the M-step."""
+        self._need_cv('smooth_run_em')
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'smooth_run_em: needs an f64 handle')
+        T = int(filt_x.shape[0])
+        if inplace and not (torch.is_tensor(filt_x) and torch.is_tensor(filt_P) and filt_x.device == self.device
+                            and filt_P.device == self.device and filt_x.is_contiguous() and filt_P.is_contiguous()
+                            and filt_x.dtype == self.torch_dtype and filt_P.dtype == self.torch_dtype):
+            raise KFError(_lib.KF_EINVAL, 'smooth_run_em: inplace needs contiguous float64 device tensors filt_x / '
+                                          'filt_P')
+        k = int(update_every)
+        if k < 1:
+            raise KFError(_lib.KF_EINVAL, f'smooth_run_em: update_every = {k} < 1')
+        U = T // k
+        fx = self._dev(filt_x, (T, self.n, self.batch), 'filt_x')
+        fP = self._dev(filt_P, (T, 3 * self.c, self.batch), 'filt_P')
+        ud = self._dev(u, (T, self.c, self.batch), 'u') if u is not None else None
+        zd = self._dev(z, (U, self.m, self.batch), 'z') if (z is not None and U > 0) else None
+        md = self._dev(mask, (U, self.batch), 'mask', torch.uint8) if (mask is not None and zd is not None) else None
+        dts = self._dev(dt_steps, (T,), 'dt_steps', torch.float64) if dt_steps is not None else None
+        if dts is None and dt is None:
+            raise ValueError('smooth_run_em: give dt (scalar) or dt_steps [T]')
+        ix = iP = six = siP = None
+        if init is not None:
+            ix = self._dev(init[0], (self.n, self.batch), 'init x')
+            iP = init[1]
+            if tuple(iP.shape) == (self.ntri, self.batch):
+                iP = self._dev(iP, (self.ntri, self.batch), 'init P')[self._block_rows()]
+            iP = self._dev(iP, (3 * self.c, self.batch), 'init P')
+            if init_out:
+                six, siP = self.empty(self.n, self.batch), self.empty(3 * self.c, self.batch)
+        sx = (fx if inplace else self.empty(T, self.n, self.batch)) if x else None
+        sP = (fP if inplace else self.empty(T, 3 * self.c, self.batch)) if P else None
+        ld = self.empty(T, self.batch) if logdet else None
+        st = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if status else None
+        et = torch.empty(_lib.KF_EM_ROWS(self.c), self.batch, dtype=torch.float64, device=self.device) if em else None
+        check(_lib.lib().kf_smooth_run_em(self.handle, T, float(dt or 0.0), _ptr(dts), _ptr(ud), _ptr(zd), _ptr(md), k,
+                                          _ptr(fx), _ptr(fP), _ptr(ix), _ptr(iP), _ptr(sx), _ptr(sP), _ptr(ld), _ptr(st),
+                                          _ptr(six), _ptr(siP), _ptr(self._cv_consts(consts)), _ptr(et), self._stream()))
+        return SmoothedEm(sx, sP, ld, st, six, siP, et)
+
+    def fit_noise(self, u, z, x0=None, consts=None, iters=10, dt=None, dt_steps=None, update_every=1, mask=None):
+        """EM for q_pos, q_vel and the diagonal of R, every filter on its own stream, on the device.
+        Each of the ``iters`` iterations restores the initial state (``reset(x0)``: x0, the handle's
+        P0), filters under the current table (``run_scores``), gathers the statistics with the
+        initial row and no smoothed record written (``smooth_run_em``) and takes the M-step
+        (``cv_em_update``); a last forward run scores the final table.  consts [2 + d, B]: the start
+        (None: the handle's q_pos, q_vel and diagonal R in every filter); u, z, dt / dt_steps,
+        update_every and mask as in ``run_rec``.  Returns NoiseFit(consts [2 + d, B], history
+        [iters + 1, 2 + d, B] (the table each forward run used: history[0] the start, history[-1]
+        the result), nll [iters + 1, B] (``innovation_nll`` of those runs) and status [B] int32 (the
+        first non-zero of any run's or smoother's status)).  The handle is left after the last
+        forward run.  Nothing inside the loop waits for the device."""
+        self._need_cv('fit_noise')
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'fit_noise: needs an f64 handle')
+        d = self.c
+        if consts is None:
+            r = [self.params.r[i * d + i] for i in range(d)]
+            consts = cv_consts_table(self.model, [(self.params.q_pos, self.params.q_vel, r)] * self.batch)
+        tab = self._cv_consts(consts).clone()
+        x0d = self._dev(x0, (self.n, self.batch), 'x0') if x0 is not None else None
+        self.reset(x0d)
+        xi, Pi = self.state()
+        init = (xi, Pi[self._block_rows()].contiguous())
+        kw = dict(dt=dt, dt_steps=dt_steps, update_every=update_every, mask=mask)
+        history, nll = [tab], []
+        status = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+
+        def note(s):
+            return torch.where(status != 0, status, s)
+
+        for _ in range(int(iters)):
+            self.reset(x0d)
+            sr = self.run_scores(u, z, consts=tab, traj=True, cov=True, **kw)
+            status = note(self.status())
+            nll.append(innovation_nll(sr.scores, self.model, 'gps'))
+            sm = self.smooth_run_em(sr.traj, sr.cov, z, u=u, init=init, consts=tab, init_out=False, **kw)
+            status = note(sm.status)
+            tab = cv_em_update(sm.em, tab, self.model)
+            history.append(tab)
+        self.reset(x0d)
+        sr = self.run_scores(u, z, consts=tab, **kw)
+        status = note(self.status())
+        nll.append(innovation_nll(sr.scores, self.model, 'gps'))
+        return NoiseFit(tab, torch.stack(history), torch.stack(nll), status)
 
     def run_host(self, u, z, dt, update_every=1, chunks=8, traj=None, logdet=None):
         """``run`` for streams that live in host memory (numpy arrays or CPU tensors, the shapes
