@@ -713,6 +713,71 @@ int kf_smooth_sweep(kf_batch* handle, int T, const uint8_t* etype, const double*
                     const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj,
                     void* sm_logdet, int32_t* sm_status, void* stream);
 
+/* Rows of kf_smooth_sweep_em's statistics table: device [KF_REF_EM_ROWS(n, m)][B] double, filter
+ * index fastest, n = 15 | 8 states, m = 3 | 2 GPS axes.
+ * rows: N_TRANS, Q[n], N_IMU, R_IMU[n], N_GPS, R_GPS[m]  (the consts table's order, a count before each block) */
+#define KF_REF_EM_N_TRANS   0
+#define KF_REF_EM_Q         1                     /* + state                   */
+#define KF_REF_EM_N_IMU(n)  (1 + (n))
+#define KF_REF_EM_R_IMU(n)  (2 + (n))             /* + state                   */
+#define KF_REF_EM_N_GPS(n)  (2 + 2 * (n))
+#define KF_REF_EM_R_GPS(n)  (3 + 2 * (n))         /* + axis                    */
+#define KF_REF_EM_ROWS(n, m) (3 + 2 * (n) + (m))  /* 36 for REF15, 21 for REF8 */
+
+/* KF_REF_EM_ROWS for `model`: 36 for KF_MODEL_REF15, 21 for KF_MODEL_REF8.  KF_EINVAL for any other
+ * model or NULL rows. */
+int kf_em_rows(int model, int* rows);
+
+/* kf_smooth_sweep that also gathers, per filter, the sufficient statistics of one EM iteration for
+ * the diagonals of Q, R_imu and R_gps (the smoothed moments are EM's E-step).  f64 KF_MODEL_REF15 /
+ * KF_MODEL_REF8 handles.  Every argument it shares with kf_smooth_sweep means what it means there
+ * (etype, dt, the record and output layouts, running in place, failure per filter, T = 1, its
+ * limits and KF_EINVAL cases), and sm_x, sm_P, sm_traj, sm_logdet and sm_status are bit for bit
+ * kf_smooth_sweep's on the same inputs.  consts NULL means the handle's constants; the Q rates are
+ * read as kf_smooth_sweep reads them, the R rows are not read.  The handle's state and status are
+ * neither read nor touched.
+ *
+ * payload [T][9] is kf_run_sweep's, updated [T][B] the record that forward sweep wrote (non-zero:
+ * filter f applied the update of event t).  Both NULL leaves the two R blocks and their counts at
+ * 0; one without the other is KF_EINVAL.
+ *
+ * em, device [KF_REF_EM_ROWS][B] double, overwritten, may be NULL.  Event 0 starts the interval:
+ * neither a transition into it nor its update is counted, nothing before it being in the record
+ * (a stream that begins with a KF_EVENT_NONE entry, as kfmi.ref15.AdaptiveSweep's does, loses
+ * nothing).  For every event t >= 1:
+ *   Transition.  Counted (N_TRANS) when etype[t] != KF_EVENT_NONE and d = dt[t] != 0.  Its noise is
+ *   w_t = x_t - F x_{t-1}.  With J = Q d P_p^-1, E[w | all data] = J (x_s[t] - x_p) and Var[w | all
+ *   data] = Q d + J (P_s[t] - P_p) J^T, from the LDL^T of P_p and the differences the smoothing step
+ *   forms anyway (the textbook lag-one form e e^T + P_s[t] + F P_s[t-1] F^T - F L - L^T F^T, L =
+ *   C_{t-1} P_s[t], is the same quantity).  Q + i: the sum over the counted transitions of (E[w]_i^2
+ *   + Var[w]_ii) / d.  A state whose q is 0 adds exactly 0.
+ *   Applied update (updated[t][f] != 0).  A fix counts in N_GPS and adds (z_i - x_s[t]_i)^2 +
+ *   P_s[t]_ii to R_GPS + i, z the payload.  An IMU event counts in N_IMU and adds the same term to
+ *   every R_IMU + i, with z the pseudo-measurement AS THE FORWARD RUN SAW IT: attitude, rate and
+ *   acceleration rows are the sensor's values, the position and velocity rows are built from the
+ *   predicted state x_p (kf_workers.py's pseudo-measurement), rebuilt here by the event step's own
+ *   expressions.  Those rows are the forward run's own "data", not an observation of the world; an
+ *   R fitted to them describes the filter, not a sensor (kfmi.ref_em_update leaves them alone by
+ *   default).
+ *   The M-step is q_i = Q_i / N_TRANS, r_imu,i = R_IMU_i / N_IMU, r_gps,i = R_GPS_i / N_GPS
+ *   (kfmi.ref_em_update).  N_TRANS depends only on etype and dt, N_IMU and N_GPS only on etype and
+ *   updated; a filter whose sm_status is not 0 has NaN in its float rows and keeps its counts.
+ *   T = 0 zeroes the table, T = 1 leaves it all zero.
+ *
+ * Bit for bit: everything is lane-local (P is block-diagonal over the axis chains and Q, R
+ * diagonal, so J is block-diagonal too) and summed in double in backward step order, so a filter's
+ * rows are the same on every run and do not depend on B, on its place in its wave, on which sm_*
+ * outputs are NULL or on running in place.  Asynchronous on `stream`, capturable; allocates
+ * nothing; no workspace, no atomics.  Limits (KF_EINVAL before anything is queued, naming this
+ * function), besides kf_smooth_sweep's: 9 T 8 < 4 GiB (payload), B < 2 GiB (a row of flags,
+ * addressed per event), the table ROWS B 8 < 2 GiB.  Not built: f32, a full (non-diagonal) Q or R,
+ * estimates of x0 / P0, the smoothed state before event 0.  The reference estimates no noise
+ * constants. */
+int kf_smooth_sweep_em(kf_batch* handle, int T, const uint8_t* etype, const double* dt, const void* payload,
+                       const uint8_t* updated, const double* consts,
+                       const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj,
+                       void* sm_logdet, int32_t* sm_status, double* em, void* stream);
+
 /* Rows of kf_run_sweep_params' consts table for `model`: 33 for KF_MODEL_REF15 (ref_q 15, ref_r_imu
  * 15, ref_r_gps 3), 18 for KF_MODEL_REF8 (8, 8, 2).  KF_EINVAL for any other model or NULL rows. */
 int kf_consts_rows(int model, int* rows);

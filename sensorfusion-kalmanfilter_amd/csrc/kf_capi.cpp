@@ -1273,23 +1273,47 @@ int kf_run_sweep_scores(kf_batch* h, int T, const uint8_t* etype, const double* 
                           n_updated, ckpt_every, ckpt_x, ckpt_P, stream, track, scores);
 }
 
-int kf_smooth_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const double* consts,
-                    const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj, void* sm_logdet,
-                    int32_t* sm_status, void* stream) {
-    const char* fn = "kf_smooth_sweep";
-    if (int rc = check_handle(h)) return rc;
+static_assert(KF_REF_EM_N_TRANS == kfmi::kRefEmNTrans && KF_REF_EM_Q == kfmi::kRefEmQ &&
+                  KF_REF_EM_ROWS(15, 3) == kfmi::ref_em_rows(15) && KF_REF_EM_ROWS(8, 2) == kfmi::ref_em_rows(8) &&
+                  KF_REF_EM_R_GPS(15) + 3 == KF_REF_EM_ROWS(15, 3) && KF_REF_EM_R_GPS(8) + 2 == KF_REF_EM_ROWS(8, 2),
+              "kf.h's EM rows are the kernel's");
+
+// kf_smooth_sweep and kf_smooth_sweep_em (fn names the caller; em: kf_smooth_sweep_em's further
+// arguments, their block filled but for `smooth`, which this function builds)
+static int smooth_sweep_impl(const char* fn, kf_batch* h, int T, const uint8_t* etype, const double* dt,
+                             const double* consts, const void* filt_x, const void* filt_P, void* sm_x, void* sm_P,
+                             void* sm_traj, void* sm_logdet, int32_t* sm_status, void* stream,
+                             kfmi::SmoothEmArgs* em = nullptr) {
+    if (!h) return fail(KF_EINVAL, "%s: null kf_batch handle", fn);
     if (!is_ref(h)) return fail(KF_EINVAL, "%s: needs a KF_MODEL_REF15 or KF_MODEL_REF8 handle", fn);
     if (h->dtype != KF_F64) return fail(KF_EINVAL, "%s: needs an f64 handle (the f32 smoother is not built)", fn);
     if (T < 0) return fail(KF_EINVAL, "%s: T = %d < 0", fn, T);
-    if (T == 0 || h->B == 0) return KF_OK;
+    if (em && !em->payload != !em->updated)
+        return fail(KF_EINVAL, "%s: payload and updated are given together or not at all", fn);
+    if (h->B == 0) return KF_OK;
+    const int model = h->model == KF_MODEL_REF15 ? 15 : 8;
+    if (em && em->em && uint64_t(kfmi::ref_em_rows(model)) * uint64_t(h->B) * 8u >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB statistics table (%d B 8)", fn, (long long)h->B,
+                    kfmi::ref_em_rows(model));
+    if (T == 0) {  // no event: every row 0
+        if (!em || !em->em) return KF_OK;
+        hipError_t e = hipMemsetAsync(em->em, 0, sizeof(double) * size_t(kfmi::ref_em_rows(model)) * size_t(h->B),
+                                      static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+    }
     if (!etype || !dt || !filt_x || !filt_P) return fail(KF_EINVAL, "%s: null etype/dt/filt_x/filt_P", fn);
+    // EM: the payload by byte range as kf_run_sweep's; the flags a [B] span per event, the event's
+    // row from a 64-bit base
+    if (em && em->payload && uint64_t(T) * 9u * 8u >= (uint64_t(1) << 32))
+        return fail(KF_EINVAL, "%s: T = %d events exceed the 4 GiB payload descriptor (9 T 8)", fn, T);
+    if (em && em->updated && uint64_t(h->B) >= (uint64_t(1) << 31))
+        return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB flag row", fn, (long long)h->B);
     // the kernel's descriptors: etype and dt by byte range (32-bit), a record row as one span whose
     // offsets keep bit 31 free for dropped lanes
     if (uint64_t(T) * 8u >= (uint64_t(1) << 32))
         return fail(KF_EINVAL, "%s: T = %d events exceed the 4 GiB dt descriptor (8 T)", fn, T);
     if (uint64_t(h->B) * 27u * 8u >= (uint64_t(1) << 31))
         return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB row span (27 B 8)", fn, (long long)h->B);
-    const int model = h->model == KF_MODEL_REF15 ? 15 : 8;
     if (consts && uint64_t(kfmi::consts_rows(model)) * uint64_t(h->B) * 8u >= (uint64_t(1) << 31))
         return fail(KF_EINVAL, "%s: B = %lld filters exceed the 2 GiB constants table (%d B 8)", fn, (long long)h->B,
                     kfmi::consts_rows(model));
@@ -1307,8 +1331,42 @@ int kf_smooth_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, 
     a.sm_status = sm_status;
     a.kc = h->kc;
     a.consts = consts;
-    hipError_t e = kfmi::launch_ref_smooth(model, a, static_cast<hipStream_t>(stream));
+    hipError_t e;
+    if (em) {
+        em->smooth = a;
+        e = kfmi::launch_ref_smooth_em(model, *em, static_cast<hipStream_t>(stream));
+    } else {
+        e = kfmi::launch_ref_smooth(model, a, static_cast<hipStream_t>(stream));
+    }
     return e == hipSuccess ? KF_OK : hip_fail(e, fn);
+}
+
+int kf_smooth_sweep(kf_batch* h, int T, const uint8_t* etype, const double* dt, const double* consts,
+                    const void* filt_x, const void* filt_P, void* sm_x, void* sm_P, void* sm_traj, void* sm_logdet,
+                    int32_t* sm_status, void* stream) {
+    return smooth_sweep_impl("kf_smooth_sweep", h, T, etype, dt, consts, filt_x, filt_P, sm_x, sm_P, sm_traj,
+                             sm_logdet, sm_status, stream);
+}
+
+int kf_smooth_sweep_em(kf_batch* h, int T, const uint8_t* etype, const double* dt, const void* payload,
+                       const uint8_t* updated, const double* consts, const void* filt_x, const void* filt_P,
+                       void* sm_x, void* sm_P, void* sm_traj, void* sm_logdet, int32_t* sm_status, double* em,
+                       void* stream) {
+    kfmi::SmoothEmArgs ea{};
+    ea.payload = payload;
+    ea.updated = updated;
+    ea.em = em;
+    return smooth_sweep_impl("kf_smooth_sweep_em", h, T, etype, dt, consts, filt_x, filt_P, sm_x, sm_P, sm_traj,
+                             sm_logdet, sm_status, stream, &ea);
+}
+
+int kf_em_rows(int model, int* rows) {
+    if (!is_ref(model))
+        return fail(KF_EINVAL, "kf_em_rows: model %d has no sweep statistics (KF_MODEL_REF15 or KF_MODEL_REF8; the "
+                               "constant-velocity table has KF_EM_ROWS(d) rows)", model);
+    if (!rows) return fail(KF_EINVAL, "kf_em_rows: null rows");
+    *rows = kfmi::ref_em_rows(model == KF_MODEL_REF15 ? 15 : 8);
+    return KF_OK;
 }
 
 int kf_consts_rows(int model, int* rows) {

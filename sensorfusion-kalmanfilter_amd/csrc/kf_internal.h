@@ -248,6 +248,19 @@ struct SmoothArgs {
     const RefConsts* kc;     // the handle's own noise constants (device), or nullptr: the reference's
     const double* consts;    // [consts_rows][B] or nullptr: kc
 };
+// kf_smooth_sweep_em (ref_smooth_kernel's EM instantiations): kf_smooth_sweep's block, untouched, and
+// what the statistics need: the stream's payload and the forward sweep's `updated` record (both or
+// neither), and the table out (may be nullptr)
+struct SmoothEmArgs {
+    SmoothArgs smooth;
+    const void* payload;     // [T][9] or nullptr
+    const uint8_t* updated;  // [T][B] or nullptr
+    double* em;              // [ref_em_rows][B] or nullptr
+};
+// rows of SmoothEmArgs::em (kf.h's KF_REF_EM_*; kf_capi.cpp asserts they agree): a count before each
+// block, the blocks in the constants table's order
+enum : int { kRefEmNTrans = 0, kRefEmQ = 1 };
+constexpr int ref_em_rows(int n) { return n == 15 ? 36 : 21; }
 
 // Time-parallel run of one filter over a long event stream (kf_run_stream): the state banks of
 // the three chunk passes and the check.  Bank layouts are the handle's ([N][B], [NBLK][B]).
@@ -598,6 +611,8 @@ hipError_t launch_ref_sweep(int model, bool f64, const SweepArgs& a, hipStream_t
 hipError_t launch_ref_tails(int model, bool f64, const SweepArgs& a, hipStream_t stream);
 // the RTS backward pass (f64 only)
 hipError_t launch_ref_smooth(int model, const SmoothArgs& a, hipStream_t stream);
+// the backward pass with the EM statistics for Q, R_imu and R_gps (kf_smooth_sweep_em)
+hipError_t launch_ref_smooth_em(int model, const SmoothEmArgs& a, hipStream_t stream);
 hipError_t launch_ref_reset(int model, bool f64, const RefArgs& a, hipStream_t stream);
 hipError_t launch_ref15_combos(bool f64, const Ref15ComboArgs& a, hipStream_t stream);
 // child_major: one wave per (parent block, child event) instead of one lane per parent

@@ -175,6 +175,13 @@ struct ConstsColumn {
     int64_t B, f;
 };
 
+// The same column where there is a table, else the handle's own constants (or the literals):
+// ref_smooth_kernel's EM instantiations, which take either
+struct ConstsOrHandle {
+    ConstsColumn col;
+    const RefConsts* kc;
+};
+
 // One lane of the 8-lanes-per-filter kernels (ref_chain_kernel, ref_sweep_kernel,
 // ref_chain_gated_kernel): which chain lane c of a group runs, where that chain's states, block
 // rows and payload columns are, its noise constants, and the event all three kernels run.  The
@@ -241,6 +248,30 @@ struct ChainLane {
                 Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(tr[k]);
             }
         if (pva) Rgps = T(tg);
+    }
+
+    // The lane of filter f under either source (ref_smooth_kernel's EM): the table's column as
+    // above or, with no table, the handle's constants converted as the CUSTOM lanes convert them
+    // (kc null: the literals).  The choice is wave-uniform.
+    __device__ __forceinline__ ChainLane(int lane, const ConstsOrHandle& src)
+        : ChainLane(lane, static_cast<const RefConsts*>(nullptr)) {
+        static_assert(!CUSTOM, "the source is chosen at run time");
+        if (src.col.table) {
+            const ChainLane t(lane, src.col);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) q[k] = t.q[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) Rimu[k] = t.Rimu[k];
+            Rgps = t.Rgps;
+        } else if (src.kc) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (xi[k] >= 0) {
+                    q[k] = T(ro(src.kc)->q[xi[k]]);
+                    Rimu[k == 0 ? 0 : k == 1 ? 3 : 5] = T(ro(src.kc)->r_imu[xi[k]]);
+                }
+            if (pva) Rgps = T(ro(src.kc)->r_gps[ca]);
+        }
     }
 
     // P[k] where the lane holds no row k: the identity (an aw lane's inert state has variance 1)

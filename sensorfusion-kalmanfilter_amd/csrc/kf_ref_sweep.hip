@@ -1,7 +1,8 @@
 // The sweep-layout kernels of the reference models, 8 lanes per filter and one wave per workgroup
 // (the lane is kf_ref_chainlane.h's): ref_sweep_kernel (kf_run_sweep, kf_run_sweep_params,
 // kf_run_sweep_scores: launch_ref_sweep; kf_run_tails: launch_ref_tails) and the RTS smoother over
-// a sweep's record, ref_smooth_kernel (kf_smooth_sweep: launch_ref_smooth).
+// a sweep's record, ref_smooth_kernel (kf_smooth_sweep: launch_ref_smooth; with the EM statistics,
+// kf_smooth_sweep_em: launch_ref_smooth_em).
 #include "kf_ref_chainlane.h"
 
 namespace kfmi {
@@ -277,6 +278,24 @@ __global__ __launch_bounds__(kSweepBlock) void ref_sweep_kernel(const SweepArgs 
 // sm_x == filt_x and sm_P == filt_P are legal.  No atomics, no LDS, no workspace.
 // A non-positive pivot of P_p or a NaN in a loaded row poisons the filter's group from that t down
 // to 0 (NaN rows, KF_ENOTSPD in sm_status); the rows above it are already stored.
+//
+// EM (kf_smooth_sweep_em; PARAMS too, the argument block is then SmoothEmArgs): the sufficient
+// statistics of the diagonal Q, R_imu and R_gps, everything under `if constexpr` or in a type that
+// is empty without it, so the other instantiations stay the instruction streams they were
+// (profiles/sweep_em/isa_compare.log).  All of it lane-local and summed in backward step order, in
+// double: the lane that smooths a chain holds that chain's Q rows and R rows (J below is
+// block-diagonal as C is), so no group_sum, no atomics, no LDS, no workspace.
+//   the transition into event t + 1 (counted when its type is not NONE and d = dt[t + 1] != 0):
+//     J = Q d P_p^-1 by the step's own L, D and reciprocals (row i: one more right-hand side),
+//     E[w | all] = J (x_s[t + 1] - x_p), Var[w | all] = Q d + J (P_s[t + 1] - P_p) J^T, and state i
+//     adds (E[w]_i^2 + Var[w]_ii) / d.  No lag-one covariance, no row t - 1.
+//   the applied update of event t + 1 (updated[t + 1][f] != 0; the byte and the lane's two payload
+//     values of that event ride in the ring): z rebuilt as ChainLane::event built it (GPS: the
+//     payload; IMU: event's own X / V / zb lines on x_p, restated here: sharing them would move
+//     event's instruction stream), then (z_i - x_s[t + 1]_i)^2 + P_s[t + 1]_ii per measured state.
+//   Event 0 starts the interval: neither its transition nor its update is counted.
+// The counts sit on lane 0 of the group; every lane stores its own rows once, after the last step,
+// NaN where the filter was poisoned (the counts stay).
 // ------------------------------------------------------------------------------------
 #ifndef KF_SMOOTH_DEPTH
 #define KF_SMOOTH_DEPTH KF_SWEEP_DEPTH
@@ -290,20 +309,43 @@ struct SmoothIn {
     double dt;
     T x[3], P[6];
 };
+// EM: the lane's two payload values of that event and the filter's `updated` byte ride along
+template <typename T>
+struct SmoothInEm : SmoothIn<T> {
+    T va, vb;
+    int up;
+};
+// EM: one lane's accumulators (kf_smooth_sweep_em)
+struct RefEmAcc {
+    int32_t ntrans = 0, ngps = 0, nimu = 0;
+    double q[3] = {0.0, 0.0, 0.0};
+    double rimu[3] = {0.0, 0.0, 0.0};
+    double rgps = 0.0;
+};
 
-template <bool PARAMS>
+__device__ __forceinline__ const SmoothArgs& smooth_args(const SmoothArgs& a) { return a; }
+__device__ __forceinline__ const SmoothArgs& smooth_args(const SmoothEmArgs& a) { return a.smooth; }
+
+// EM: column f of the table or, without one, the handle's constants: one pair of instantiations
+// serves every handle (ChainLane's ConstsOrHandle constructor)
+template <bool PARAMS, bool EM = false>
 __device__ __forceinline__ auto smooth_consts(const SmoothArgs& a, int64_t f) {
-    if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
+    if constexpr (EM) return ConstsOrHandle{{a.consts, a.B, f}, a.kc};
+    else if constexpr (PARAMS) return ConstsColumn{a.consts, a.B, f};
     else return a.kc;
 }
 
-template <typename T, class M, bool CUSTOM, bool PARAMS = false>
-__global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArgs a) {
+template <typename T, class M, bool CUSTOM, bool PARAMS = false, bool EM = false, int DEPTH = kSmoothDepth,
+          typename A = SmoothArgs>
+__global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const A ka) {
     static_assert(!PARAMS || !CUSTOM, "per-filter constants in place of the handle's");
+    static_assert(PARAMS || !EM, "EM takes its constants as PARAMS does (or, without a table, the handle's)");
+    static_assert(std::is_same_v<A, std::conditional_t<EM, SmoothEmArgs, SmoothArgs>>, "EM: its own argument block");
+    const SmoothArgs& a = smooth_args(ka);
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kSweepBlock + threadIdx.x;
     const int64_t f = g / kGroup;
     if (f >= a.B) return;  // whole groups leave together
-    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), smooth_consts<PARAMS>(a, f));
+    const ChainLane<T, M, CUSTOM> L(static_cast<int>(g % kGroup), smooth_consts<PARAMS, EM>(a, f));
     const int c = L.c;
     const bool live = L.live;
     const uint32_t off = uint32_t(f) * uint32_t(sizeof(T));
@@ -374,13 +416,25 @@ __global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArg
     store_row(T_ - 1);
 
     const int n = T_ - 1;  // backward steps; step s is row t = T - 2 - s (past the end: row 0 again)
-    auto load = [&](int s, SmoothIn<T>& in) {
+    using In = std::conditional_t<EM, SmoothInEm<T>, SmoothIn<T>>;
+    struct NoEm {};
+    std::conditional_t<EM, RefEmAcc, NoEm> em;
+    auto load = [&](int s, In& in) {
         const int t = T_ - 2 - (s < n ? s : n - 1);
         in.type = int(__builtin_amdgcn_raw_buffer_load_b8(r_et, uint32_t(t + 1), 0, 0));
         in.dt = ldv(r_dt, uint32_t(t + 1) * 8u, 0.0);
         load_row(t, in.x, in.P);
+        if constexpr (EM) {
+            // event t + 1's measurement, the ring's last loads: the lane's two payload columns
+            // (ref_sweep_kernel's) by byte range, and the filter's byte of row t + 1 of `updated`, a
+            // [B] span from a 64-bit base per event (null streams: zero-length ranges, 0)
+            const auto r_pay = bytes_rsrc(ka.payload, S * 9u * uint32_t(sizeof(T)));
+            in.va = ldv(r_pay, (uint32_t(t + 1) * 9u + uint32_t(L.ia)) * uint32_t(sizeof(T)), T(0));
+            in.vb = ldv(r_pay, (uint32_t(t + 1) * 9u + uint32_t(L.ib)) * uint32_t(sizeof(T)), T(0));
+            in.up = int(__builtin_amdgcn_raw_buffer_load_b8(span_rsrc(ka.updated, t + 1, uint32_t(a.B), 1), uint32_t(f), 0, 0));
+        }
     };
-    auto step = [&](int s, const SmoothIn<T>& in) {
+    auto step = [&](int s, const In& in) {
         const int t = T_ - 2 - s;
         const int type = wave_uniform(in.type);  // every lane loaded the same type and dt
         bool bad = is_nan_row(in.x, in.P);
@@ -427,6 +481,48 @@ __global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArg
             for (int k = 0; k < 3; ++k) dx[k] = xs[0][k] - xp[0][k];
 #pragma unroll
             for (int k = 0; k < 6; ++k) D[k] = Ps[k] - Pp[k];
+            if constexpr (EM) {
+                // the transition into event t + 1; one of no duration carries no noise and is not
+                // counted (wave-uniform).  Row i of J: P_p j = q_i d e_i
+                const bool count = in.dt != 0.0;
+                const T inv_d = T(1) / (count ? dt : T(1));
+                em.ntrans += count ? 1 : 0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const T qd = L.q[i] * dt;
+                    const T w0 = i == 0 ? qd : T(0);
+                    const T w1 = i == 1 ? qd : fmaT(-l10, w0, T(0));
+                    const T w2 = i == 2 ? qd : fmaT(-l21, w1, fmaT(-l20, w0, T(0)));
+                    const T j2 = w2 * i2;
+                    const T j1 = fmaT(-l21, j2, w1 * i1);
+                    const T j0 = fmaT(-l20, j2, fmaT(-l10, j1, w0 * i0));
+                    const T ew = fmaT(j2, dx[2], fmaT(j1, dx[1], j0 * dx[0]));
+                    const T jd0 = fmaT(j2, D[tri<3>(2, 0)], fmaT(j1, D[tri<3>(1, 0)], j0 * D[tri<3>(0, 0)]));
+                    const T jd1 = fmaT(j2, D[tri<3>(2, 1)], fmaT(j1, D[tri<3>(1, 1)], j0 * D[tri<3>(0, 1)]));
+                    const T jd2 = fmaT(j2, D[tri<3>(2, 2)], fmaT(j1, D[tri<3>(1, 2)], j0 * D[tri<3>(0, 2)]));
+                    const T var = fmaT(jd2, j2, fmaT(jd1, j1, fmaT(jd0, j0, qd)));
+                    em.q[i] += count ? double(fmaT(ew, ew, var) * inv_d) : 0.0;
+                }
+                // the applied update of event t + 1 against the smoothed row t + 1, still in xs / Ps:
+                // z as the forward step built it from x_p (ChainLane::event's lines)
+                if (in.up != 0 && (type == kGps || type == kImu)) {
+                    if (type == kGps) {
+                        const T e = in.va - xs[0][0];
+                        em.rgps += double(fmaT(e, e, Ps[0]));
+                        em.ngps += 1;
+                    } else {
+                        const T V = fmaT(in.vb, dt, xp[0][1]);
+                        const T X = fmaT(V, dt, xp[0][0]);
+                        const T z[3] = {L.pva ? X : in.va, L.pva ? V : in.vb, L.pva ? in.vb : T(0)};
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            const T e = z[k] - xs[0][k];
+                            em.rimu[k] += double(fmaT(e, e, Ps[tri<3>(k, k)]));
+                        }
+                        em.nimu += 1;
+                    }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 xs[0][i] = fmaT(C[i][2], dx[2], fmaT(C[i][1], dx[1], fmaT(C[i][0], dx[0], in.x[i])));
@@ -451,10 +547,32 @@ __global__ __launch_bounds__(kSweepBlock) void ref_smooth_kernel(const SmoothArg
         if (group_any(live && bad) || st != 0) poison();
         store_row(t);
     };
-    ring_run<kSmoothDepth, T, SmoothIn<T>>(n, load, step);
+    ring_run<DEPTH, T, In>(n, load, step);
     if (a.sm_status) {
         const auto rs = span_rsrc(a.sm_status, 0, uint32_t(a.B) * 4u, 1);
         __builtin_amdgcn_raw_buffer_store_b32(uint32_t(st), rs, c == 0 ? uint32_t(f) * 4u : kDropOffset, 0, 0);
+    }
+    if constexpr (EM) {
+        // rows KF_REF_EM_* of column f, one span (row r at (r B + f) 8; ROWS B 8 < 2^31, checked by
+        // the caller): lane 0 the counts, every lane its states' Q and R_imu rows, a pva lane its
+        // axis' R_gps row; a filter that failed keeps its counts only.  A null table: nothing stored
+        if (ka.em != nullptr) {  // wave-uniform
+            constexpr int kRows = ref_em_rows(M::N);
+            const auto re = span_rsrc(ka.em, 0, uint32_t(a.B) * 8u, kRows);
+            const uint32_t rb8 = uint32_t(a.B) * 8u, off8 = uint32_t(f) * 8u;
+            const double nanv = quiet_nan<double>();
+            const bool good = st == 0;
+            auto at = [&](bool have, int row) { return have ? uint32_t(row) * rb8 + off8 : kDropOffset; };
+            stv(re, at(c == 0, kRefEmNTrans), double(em.ntrans));
+            stv(re, at(c == 0, 1 + M::N), double(em.nimu));
+            stv(re, at(c == 0, 2 + 2 * M::N), double(em.ngps));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                stv(re, at(L.xi[k] >= 0, kRefEmQ + L.xi[k]), good ? em.q[k] : nanv);
+                stv(re, at(L.xi[k] >= 0, 2 + M::N + L.xi[k]), good ? em.rimu[k] : nanv);
+            }
+            stv(re, at(L.pva, 3 + 2 * M::N + L.ca), good ? em.rgps : nanv);
+        }
     }
 }
 }  // namespace
@@ -488,6 +606,28 @@ hipError_t launch_ref_smooth(int model, const SmoothArgs& a, hipStream_t stream)
     else
         KF_REF_DISPATCH(model, true, a.kc, if constexpr (sizeof(T) == 8)
                                                ref_smooth_kernel<T, M, CUSTOM><<<grid, kSweepBlock, 0, stream>>>(a));
+    return hipGetLastError();
+}
+
+// kf_smooth_sweep_em's instantiations: their input ring holds two payload values and the `updated`
+// byte more per step.  Depths 2 and 4 were A/B-measured in one process on the 583k-event log at B = 64
+// (profiles/sweep_em/sweep_em_timing.log): 655 / 585 ms (every output / table only) at 4 against
+// 763 / 673 ms at 2, so 4, the smoother's own depth.  Running in place is legal at any depth: a
+// step stores row t alone, after its own load of that row, and the rows still to be loaded lie below t
+#ifndef KF_REF_EM_DEPTH
+#define KF_REF_EM_DEPTH 4
+#endif
+
+hipError_t launch_ref_smooth_em(int model, const SmoothEmArgs& e, hipStream_t stream) {
+    const SmoothArgs& a = e.smooth;
+    if (a.B <= 0 || a.T <= 0 || (model != 15 && model != 8) || !a.filt_x || !a.filt_P || !a.etype || !a.dt ||
+        !e.payload != !e.updated)
+        return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>((a.B * kGroup + kSweepBlock - 1) / kSweepBlock));
+    if (model == 15)
+        ref_smooth_kernel<double, M15, false, true, true, KF_REF_EM_DEPTH, SmoothEmArgs><<<grid, kSweepBlock, 0, stream>>>(e);
+    else
+        ref_smooth_kernel<double, M8, false, true, true, KF_REF_EM_DEPTH, SmoothEmArgs><<<grid, kSweepBlock, 0, stream>>>(e);
     return hipGetLastError();
 }
 

@@ -66,6 +66,31 @@ def KF_EM_ROWS(d):
     return 4 + d
 
 
+# rows of kf_smooth_sweep_em's table for a model of n states and m GPS axes (kf.h's KF_REF_EM_*)
+KF_REF_EM_N_TRANS = 0
+KF_REF_EM_Q = 1
+
+
+def KF_REF_EM_N_IMU(n):
+    return 1 + n
+
+
+def KF_REF_EM_R_IMU(n):
+    return 2 + n
+
+
+def KF_REF_EM_N_GPS(n):
+    return 2 + 2 * n
+
+
+def KF_REF_EM_R_GPS(n):
+    return 3 + 2 * n
+
+
+def KF_REF_EM_ROWS(n, m):
+    return 3 + 2 * n + m
+
+
 KF_OPT_PREDICT = 1
 KF_OPT_CV_KERNEL = 2
 KF_OPT_BLOCKS_PER_CU = 3
@@ -153,6 +178,8 @@ SIGNATURES = {
     'kf_run_sweep_params': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_run_sweep_scores': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'kf_smooth_sweep': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kf_smooth_sweep_em': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kf_em_rows': (_i, [_i, ctypes.POINTER(_i)]),
     'kf_consts_rows': (_i, [_i, ctypes.POINTER(_i)]),
     'kf_run_tails': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
     'kf_stream_check': (_i, [_vp, _vp, _vp]),

@@ -92,6 +92,7 @@ assert len(SCORE_ROWS) == _lib.KF_SCORE_ROWS
 
 SweepScores = collections.namedtuple('SweepScores', 'scores n_updated traj logdet updated ckpt_x ckpt_P')
 SmoothedSweep = collections.namedtuple('SmoothedSweep', 'x P traj logdet status')
+SmoothedSweepEm = collections.namedtuple('SmoothedSweepEm', 'x P traj logdet status em')
 SmoothedRun = collections.namedtuple('SmoothedRun', 'x P logdet status')
 RunSmoothed = collections.namedtuple('RunSmoothed', 'traj cov logdet smoothed')
 ScoredRun = collections.namedtuple('ScoredRun', 'scores traj cov logdet')
@@ -147,6 +148,65 @@ def cv_em_update(em, consts, model):
     for row, src in ((_lib.KF_CV_CONST_Q_POS, _lib.KF_EM_Q_POS), (_lib.KF_CV_CONST_Q_VEL, _lib.KF_EM_Q_VEL)):
         out[row] = torch.where(n_tr > 0, e[src] / (d * n_tr), c[row])
     out[_lib.KF_CV_CONST_R:] = torch.where(n_fix > 0, e[_lib.KF_EM_R:] / n_fix, c[_lib.KF_CV_CONST_R:])
+    return out.numpy() if as_array else out
+
+
+def em_rows(model):
+    """Rows of smooth_sweep_em's table for a reference model (kf_em_rows): 36 for 'ref15', 21 for
+    'ref8'."""
+    n = ctypes.c_int(0)
+    check(_lib.lib().kf_em_rows(MODELS[model][0], ctypes.byref(n)))
+    return n.value
+
+
+def ref_em_rows(model):
+    """Where smooth_sweep_em's blocks start for 'ref15' / 'ref8' (kf.h's KF_REF_EM_*): a dict of
+    n_trans, q, n_imu, r_imu, n_gps, r_gps ('q', 'r_imu', 'r_gps': the first of n, n, m rows) and
+    rows, the table's height."""
+    if model not in REF_MODELS:
+        raise KFError(_lib.KF_EINVAL, f'ref_em_rows: model {model!r} is not ref15 / ref8')
+    n, m = MODELS[model][1], MODELS[model][2]
+    return {'n_trans': _lib.KF_REF_EM_N_TRANS, 'q': _lib.KF_REF_EM_Q, 'n_imu': _lib.KF_REF_EM_N_IMU(n),
+            'r_imu': _lib.KF_REF_EM_R_IMU(n), 'n_gps': _lib.KF_REF_EM_N_GPS(n), 'r_gps': _lib.KF_REF_EM_R_GPS(n),
+            'rows': _lib.KF_REF_EM_ROWS(n, m)}
+
+
+# the states whose IMU pseudo-measurement row is the sensor's own value (attitude, rate,
+# acceleration); the position and velocity rows are built from the predicted state
+IMU_MEASURED = {'ref15': (3, 4, 5, 9, 10, 11, 12, 13, 14), 'ref8': (2, 5, 6, 7)}
+
+
+def ref_em_update(em, consts, model, imu_rows='measured'):
+    """EM's M-step on smooth_sweep_em's statistics, per filter, in torch where the tables live: from
+    em [ROWS, B] and the table consts [R, B] (run_sweep's, the one it was gathered under), the new
+    table with q_i = Q_i / N_TRANS, r_imu,i = R_IMU_i / N_IMU and r_gps,i = R_GPS_i / N_GPS.  A zero
+    count keeps the old values of its block, and a q row whose old value is 0 stays 0 (the model's
+    way of saying the state has no process noise).  ``imu_rows``: 'measured' (the default) updates
+    only the R_imu rows whose z is sensor data (attitude, rate, acceleration: IMU_MEASURED) and keeps
+    the position and velocity rows, whose z the forward run built from its own predicted state;
+    'all' updates every row; 'none' leaves R_imu alone.  Tensors (any device) or arrays; the result
+    is of consts' kind.  A failed filter's NaN rows pass through."""
+    if model not in REF_MODELS:
+        raise KFError(_lib.KF_EINVAL, f'ref_em_update: model {model!r} is not ref15 / ref8')
+    if imu_rows not in ('measured', 'all', 'none'):
+        raise KFError(_lib.KF_EINVAL, f"ref_em_update: imu_rows {imu_rows!r} is not 'measured', 'all' or 'none'")
+    n, m = MODELS[model][1], MODELS[model][2]
+    r = ref_em_rows(model)
+    as_array = not torch.is_tensor(consts)
+    c = torch.as_tensor(consts, dtype=torch.float64)
+    e = torch.as_tensor(em, dtype=torch.float64).to(c.device)
+    if e.ndim != 2 or c.ndim != 2 or e.shape[0] != r['rows'] or c.shape[0] != 2 * n + m or e.shape[1] != c.shape[1]:
+        raise KFError(_lib.KF_EINVAL, f'ref_em_update: em {tuple(e.shape)} / consts {tuple(c.shape)}, expected '
+                                      f'({r["rows"]}, B) / ({2 * n + m}, B)')
+    n_tr, n_imu, n_gps = e[r['n_trans']], e[r['n_imu']], e[r['n_gps']]
+    out = c.clone()
+    q_old = c[:n]
+    out[:n] = torch.where((n_tr > 0) & (q_old != 0), e[r['q']:r['q'] + n] / n_tr, q_old)
+    if imu_rows != 'none':
+        rows = list(range(n)) if imu_rows == 'all' else list(IMU_MEASURED[model])
+        idx = torch.as_tensor(rows, device=c.device)
+        out[n + idx] = torch.where(n_imu > 0, e[r['r_imu'] + idx] / n_imu, c[n + idx])
+    out[2 * n:] = torch.where(n_gps > 0, e[r['r_gps']:r['r_gps'] + m] / n_gps, c[2 * n:])
     return out.numpy() if as_array else out
 
 
@@ -895,6 +955,45 @@ class BatchedKF:
         check(_lib.lib().kf_smooth_sweep(self.handle, T, _ptr(et), _ptr(dtd), _ptr(tab), _ptr(fx), _ptr(fP), _ptr(sx),
                                          _ptr(sP), _ptr(tr), _ptr(ld), _ptr(st), self._stream()))
         return SmoothedSweep(sx, sP, tr, ld, st)
+
+    def smooth_sweep_em(self, etype, dt, payload, updated, filt_x, filt_P, consts=None, x=True, P=False, traj=False,
+                        logdet=False, status=True, em=True, inplace=False):
+        """smooth_sweep that also gathers the EM statistics for the diagonals of Q, R_imu and R_gps,
+        per filter (kf_smooth_sweep_em).  etype, dt, filt_x, filt_P, consts, x, P, traj, logdet and
+        inplace are smooth_sweep's, and those outputs are its bits; ``payload`` [T, 9] is run_sweep's
+        and ``updated`` [T, B] uint8 the record that forward sweep wrote (both None: only the Q
+        rows are gathered).  Returns SmoothedSweepEm(x, P, traj, logdet, status, em), None where not
+        asked for; ``em`` is a [ROWS, B] float64 tensor (ref_em_rows(model): a count before each of
+        the blocks Q [n], R_imu [n], R_gps [m]; event 0 starts the interval and is not counted),
+        whose M-step is kfmi.ref_em_update.  A filter that failed has NaN in its float rows and
+        keeps its counts."""
+        if self.model not in REF_MODELS:
+            raise ValueError('smooth_sweep_em needs a ref15 or ref8 handle')
+        if self.dtype != 'f64':
+            raise KFError(_lib.KF_EINVAL, 'smooth_sweep_em: needs an f64 handle')
+        if (payload is None) != (updated is None):
+            raise KFError(_lib.KF_EINVAL, 'smooth_sweep_em: payload and updated are given together or not at all')
+        T = int(etype.shape[0])
+        if inplace and not (torch.is_tensor(filt_x) and torch.is_tensor(filt_P) and filt_x.device == self.device
+                            and filt_P.device == self.device and filt_x.is_contiguous() and filt_P.is_contiguous()):
+            raise KFError(_lib.KF_EINVAL, 'smooth_sweep_em: inplace needs contiguous device tensors filt_x / filt_P')
+        fx = self._dev(filt_x, (T, self.n, self.batch), 'filt_x')
+        fP = self._dev(filt_P, (T, self.ntri, self.batch), 'filt_P')
+        tab = self._consts_tab(consts) if consts is not None else None
+        et = self._dev(etype.reshape(T), (T,), 'etype', torch.uint8)
+        dtd = self._dev(dt.reshape(T), (T,), 'dt', torch.float64)
+        pay = self._dev(payload.reshape(T, 9), (T, 9), 'payload') if payload is not None else None
+        up = self._dev(updated, (T, self.batch), 'updated', torch.uint8) if updated is not None else None
+        sx = (fx if inplace else self.empty(T, self.n, self.batch)) if x else None
+        sP = (fP if inplace else self.empty(T, self.ntri, self.batch)) if P else None
+        tr = self.empty(T, TRAJ_WIDTH[self.model], self.batch) if traj else None
+        ld = self.empty(T, self.batch) if logdet else None
+        st = torch.zeros(self.batch, dtype=torch.int32, device=self.device) if status else None
+        tb = torch.empty(em_rows(self.model), self.batch, dtype=torch.float64, device=self.device) if em else None
+        check(_lib.lib().kf_smooth_sweep_em(self.handle, T, _ptr(et), _ptr(dtd), _ptr(pay), _ptr(up), _ptr(tab),
+                                            _ptr(fx), _ptr(fP), _ptr(sx), _ptr(sP), _ptr(tr), _ptr(ld), _ptr(st),
+                                            _ptr(tb), self._stream()))
+        return SmoothedSweepEm(sx, sP, tr, ld, st, tb)
 
     def run_tails(self, etype, dt, payload, lo, hi, thresholds, src_x=None, src_P=None, src_row=None, src_col=None,
                   counts=False):

@@ -606,12 +606,22 @@ class AdaptiveSweep:
     they are:
         states, _ = AdaptiveSweep(events, [-np.inf], smooth=True).smoothed(0)
         track = (np.array([s[0] for s in states]), np.array([s[1:4] for s in states]))
-        ParameterSweep(events, sets, scores=True, track=track).best('pos_rmse')"""
+        ParameterSweep(events, sets, scores=True, track=track).best('pos_rmse')
+
+    ``em=True`` (needs smooth) makes the backward launch kf_smooth_sweep_em: the forward launch also
+    records ``updated`` (even with records=False), and ``.em`` is the EM statistics for the
+    diagonals of Q, R_imu and R_gps, a NumPy [36, B] table (engine.ref_em_rows('ref15'); the leading
+    NONE entry makes "event 0 is not counted" lossless here).  ``.em_update(imu_rows='measured')``:
+    the list of B ModelConsts after one M-step (engine.ref_em_update), each keeping its set's P0.
+    fit_noise iterates it."""
 
     def __init__(self, events, thresholds, start_idx=None, end_idx=None, initial_pt=None, initial_state=None,
                  dtype='f64', device=0, consts=None, records=True, checkpoint_every=4096, scores=False, track=None,
-                 smooth=False):
+                 smooth=False, em=False, _run=True):
         from .ingest import events_dt
+        self.em = None
+        if em and not smooth:
+            raise ValueError('em=True needs smooth=True (the statistics are the smoother\'s)')
         self.thresholds = np.array(thresholds, dtype=np.float64).reshape(-1)
         self.dtype, self.consts, self.records = dtype, consts, bool(records)
         self.scored, self.scores = bool(scores), None
@@ -724,37 +734,52 @@ class AdaptiveSweep:
             rows = track_positions(tt, tp, self._t)
             rows[~self._keep] = np.nan
             self._track = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+        if not _run:  # fit_noise: the window's arrays only
+            return
         if smooth:
             # the filtered record (15 + 27 rows) and the smoothed records kept, 8 B each per entry and filter
-            rows = 15 + 27 + 6 + 1 + (27 if smooth == 'full' else 0)
-            need = (T + 1) * rows * B * 8
-            free = torch.cuda.mem_get_info(dev)[0]
-            if need > free:
-                raise _lib.KFError(_lib.KF_ENOMEM, f'smooth: the filtered and smoothed records of {T + 1} entries x '
-                                                   f'{B} filters need {need} B, the device has {free} B free')
+            _smooth_memory_check(dev, T + 1, B, 15 + 27 + 6 + 1 + (27 if smooth == 'full' else 0))
+        need_up = self.records or bool(em)
         kf = BatchedKF('ref15', B, dtype, device=dev.index or 0, params=_params(consts))
         try:
             kf.set_state(self._x0.expand(15, B).contiguous(), self._P0.expand(27, B).contiguous())
             if self.scored:
                 r = kf.run_sweep_scores(self._et, self._dt, self._pay, self._table, torch.from_numpy(self.thresholds),
                                         track=self._track, traj=self.records, logdet=self.records,
-                                        updated=self.records, checkpoint_every=self.every)
+                                        updated=need_up, checkpoint_every=self.every)
                 self._traj, self._ld, self._up, nu, self._cx, self._cP = (r.traj, r.logdet, r.updated, r.n_updated,
                                                                           r.ckpt_x, r.ckpt_P)
                 self.scores = _scores_dict(r.scores.cpu().numpy())
             else:
                 (self._traj, self._ld, self._up, nu, self._cx, self._cP) = kf.run_sweep(
                     self._et, self._dt, self._pay, torch.from_numpy(self.thresholds), traj=self.records,
-                    logdet=self.records, updated=self.records, checkpoint_every=self.every, consts=self._table)
+                    logdet=self.records, updated=need_up, checkpoint_every=self.every, consts=self._table)
             self._x, self._Pb = kf.state()
             self._status = kf.status()
             self.n_updates = nu.cpu().numpy().astype(np.int64)
-            if smooth:
+            if smooth and em:
+                sm = kf.smooth_sweep_em(self._et, self._dt, self._pay, self._up, self._cx, self._cP,
+                                        consts=self._table, x=False, P=smooth == 'full', traj=True, logdet=True)
+                self.em = sm.em.cpu().numpy()
+            elif smooth:
                 sm = kf.smooth_sweep(self._et, self._dt, self._cx, self._cP, consts=self._table, x=False,
                                      P=smooth == 'full', traj=True, logdet=True)
+            if smooth:
                 self._sm_traj, self._sm_ld, self._sm_P, self._sm_status = sm.traj, sm.logdet, sm.P, sm.status
         finally:
             kf.close()
+
+    def em_update(self, imu_rows='measured'):
+        """One M-step on ``.em`` (needs em=True): the list of B ModelConsts, filter i's constants
+        after engine.ref_em_update with its own P0 kept.  ``imu_rows``: 'measured' | 'all' | 'none'."""
+        from .engine import ref_em_update
+        if self.em is None:
+            raise ValueError('em_update needs em=True and a window that ran')
+        sets = getattr(self, '_sets', None) or [self.consts if self.consts is not None else ModelConsts('ref15')] * \
+            len(self.thresholds)
+        new = ref_em_update(self.em, consts_table('ref15', sets), 'ref15', imu_rows)
+        return [ModelConsts('ref15', q=new[:15, f], r_imu=new[15:30, f], r_gps=new[30:, f], p0=c.p0)
+                for f, c in enumerate(sets)]
 
     def smoothed(self, i):
         """(states, logdets) of the fixed-interval smoother over thresholds[i]'s run (needs
@@ -888,6 +913,16 @@ class AdaptiveSweep:
         return out
 
 
+def _smooth_memory_check(dev, entries, B, rows):
+    """KFError(KF_ENOMEM) before anything runs if ``rows`` float64 rows per entry and filter do not
+    fit the device's free memory (the smoothed sweeps' records)."""
+    need = entries * rows * B * 8
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free:
+        raise _lib.KFError(_lib.KF_ENOMEM, f'smooth: the filtered and smoothed records of {entries} entries x '
+                                           f'{B} filters need {need} B, the device has {free} B free')
+
+
 def _scores_dict(table):
     """run_sweep_scores' [8, B] table as the sweeps' ``scores``: the counts, sums and innovation
     negative log-likelihoods per sensor, pos_n and pos_rmse = sqrt(pos_sse / pos_n)."""
@@ -946,7 +981,7 @@ class ParameterSweep(AdaptiveSweep):
 
     def __init__(self, events, consts_list, thresholds=None, start_idx=None, end_idx=None, initial_pt=None,
                  initial_state=None, dtype='f64', device=0, records=True, checkpoint_every=4096, track=None,
-                 scores=False, smooth=False):
+                 scores=False, smooth=False, em=False, _run=True):
         self._sets = list(consts_list)
         if thresholds is None:
             thresholds = np.full(len(self._sets), -np.inf)
@@ -957,13 +992,78 @@ class ParameterSweep(AdaptiveSweep):
             if not isinstance(c, ModelConsts) or c.model != 'ref15':
                 raise ValueError('ParameterSweep: consts_list holds ModelConsts(\'ref15\', ...)')
         super().__init__(events, thresholds, start_idx, end_idx, initial_pt, initial_state, dtype, device, None,
-                         records, checkpoint_every, scores, track, smooth=smooth)
+                         records, checkpoint_every, scores, track, smooth=smooth, em=em, _run=_run)
         self.consts_list = self._sets
 
     def warm_starts(self, index, end_idxs):
         if len(index) != len(end_idxs):
             raise ValueError(f'warm_starts: {len(index)} constant sets for {len(end_idxs)} end points')
         return [self.warm_start(int(i), e) for i, e in zip(index, end_idxs)]
+
+
+def fit_noise(events, consts_list=None, thresholds=None, iters=10, imu_rows='measured', **window):
+    """EM for the diagonals of Q, R_imu and R_gps of the 15-state model over ONE log: the B starting
+    sets of ``consts_list`` (ModelConsts('ref15', ...); None: the reference's alone) each run their
+    own EM, filter i gated by thresholds[i] (None: no gate).  ``window``: ParameterSweep's start_idx,
+    end_idx, initial_pt, initial_state, device.  Every iteration is one scored forward sweep
+    (kf_run_sweep_scores with ckpt_every = 1 and ``updated``), one kf_smooth_sweep_em in place over
+    its record, and engine.ref_em_update(imu_rows=...); the tables stay on the device.  The start
+    state and each set's P0 are kept (x0 / P0 are not estimated).
+
+    Returns engine.NoiseFit(consts, history, nll, status): the B fitted ModelConsts, history
+    [iters + 1, 33, B] (the table every iteration started from, then the result), nll [iters + 1,
+    B] (the GPS + IMU innovation negative log-likelihood of every forward sweep, so before each
+    update, plus one more sweep that scores the last table) and status [B] (the last backward
+    pass'; a filter that failed keeps NaN constants from there on).
+
+    Unlike the constant-velocity loop (BatchedKF.fit_noise) this is not textbook EM on fixed data:
+    the IMU pseudo-measurement's position and velocity rows are built from the predicted state, so
+    the "data" move with the constants, and under a finite threshold the gate decides which updates
+    exist at all, so the likelihood's terms change from one iteration to the next.  The NLL need
+    not fall monotonically under a finite threshold or with imu_rows='all'; read ``nll`` before
+    trusting a fit."""
+    from .engine import NoiseFit, innovation_nll, ref_em_update
+    sets = [ModelConsts('ref15')] if consts_list is None else list(consts_list)
+    if iters < 0:
+        raise ValueError(f'fit_noise: iters = {iters} < 0')
+    for k in ('dtype', 'records', 'scores', 'smooth', 'em', 'checkpoint_every', 'track'):
+        if k in window:
+            raise ValueError(f'fit_noise: {k} is not a window argument (start_idx, end_idx, initial_pt, '
+                             f'initial_state, device)')
+    sw = ParameterSweep(events, sets, thresholds, dtype='f64', records=False, _run=False, **window)
+    B = len(sets)
+    tab = torch.from_numpy(consts_table('ref15', sets))
+    if sw.empty:  # a cold window without a fix: nothing to fit
+        return NoiseFit(sets, tab.numpy()[None], np.zeros((1, B)), np.zeros(B, np.int32))
+    dev = sw.dev
+    T = int(sw._et.shape[0])
+    _smooth_memory_check(dev, T, B, 15 + 27)
+    tab = tab.to(dev)
+    thr = torch.from_numpy(sw.thresholds)
+    x0, P0 = sw._x0.expand(15, B).contiguous(), sw._P0.expand(27, B).contiguous()
+    history, nll = [tab], []
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def forward(kf, tab, record):
+        kf.set_state(x0, P0)
+        r = kf.run_sweep_scores(sw._et, sw._dt, sw._pay, tab, thr, updated=record, checkpoint_every=1 if record else 0)
+        nll.append(innovation_nll(r.scores, 'ref15', 'gps') + innovation_nll(r.scores, 'ref15', 'imu'))
+        return r
+
+    with BatchedKF('ref15', B, 'f64', device=dev.index or 0) as kf:
+        for _ in range(iters):
+            r = forward(kf, tab, True)
+            sm = kf.smooth_sweep_em(sw._et, sw._dt, sw._pay, r.updated, r.ckpt_x, r.ckpt_P, consts=tab, x=True, P=True,
+                                    inplace=True)
+            status = sm.status
+            tab = ref_em_update(sm.em, tab, 'ref15', imu_rows)
+            history.append(tab)
+            del r, sm
+        forward(kf, tab, False)
+    hist = torch.stack(history).cpu().numpy()
+    fitted = [ModelConsts('ref15', q=hist[-1, :15, f], r_imu=hist[-1, 15:30, f], r_gps=hist[-1, 30:, f], p0=c.p0)
+              for f, c in enumerate(sets)]
+    return NoiseFit(fitted, hist, torch.stack(nll).cpu().numpy(), status.cpu().numpy())
 
 
 def run_parameter_sweep(events, consts_list, thresholds=None, **kw):
