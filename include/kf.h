@@ -1092,7 +1092,11 @@ typedef struct kf_ingest_info {
  * src [N] (position in utm_data for a fix, IMU row index), zone_number [N], zone_letter [N]
  * (0 for IMU rows); src/zone_* may be NULL.  Events are ordered by time, fixes first on ties
  * (Python's stable sort, kf_workers.py:384).  Synchronous (the event count is returned).
- * KF_EINVAL when no GPS row has a latitude (the reference's biases are undefined then). */
+ * KF_EINVAL when no GPS row has a latitude (the reference's biases are undefined then).
+ * KF_EINVAL when the time of a kept fix or of an IMU row is NaN or +-inf: such a key has no
+ * place in the merge (it would sort level with or past the dropped fixes).  The error text names
+ * the sensor and the lowest such row (GPS first); no output row is written.  The time of a
+ * dropped GPS row is never looked at, as the reference never parses it. */
 int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* imu, int64_t n_imu, int64_t ld_imu,
               int flags, const double* bias, uint8_t* etype, double* t, double* payload, int32_t* src,
               int8_t* zone_number, char* zone_letter, kf_ingest_info* info, void* stream);

@@ -117,7 +117,8 @@ struct IngestArgs {
     int8_t* zone;               // [n_gps] zone number (0: not kept)
     char* letter;
     int32_t* keep;              // [n_gps] 0/1
-    unsigned long long* first;  // [2]: first row with a latitude, first kept row
+    unsigned long long* first;  // [4]: first row with a latitude, first kept row, first kept fix
+                                //      and first IMU row whose time is NaN or +-inf
     double* bias;               // [6]: angular velocity, linear acceleration
     double* keys;               // [n_gps + n_imu]
     int32_t* vals;
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(kIngBlock) void fix_kernel(const IngestArgs a) {
     char zl = 0;
     if (kept) {
         atomicMin(&a.first[1], static_cast<unsigned long long>(i));
+        if (!isfinite(t)) atomicMin(&a.first[2], static_cast<unsigned long long>(i));
         utm_from_latlon(lat, lon, e, n, zn, zl);
     }
     a.east[i] = e;
@@ -152,7 +154,9 @@ __global__ __launch_bounds__(kIngBlock) void fix_kernel(const IngestArgs a) {
 __global__ __launch_bounds__(kIngBlock) void imu_keys_kernel(const IngestArgs a) {
     const int64_t j = int64_t(blockIdx.x) * kIngBlock + threadIdx.x;
     if (j >= a.n_imu) return;
-    a.keys[a.n_gps + j] = a.imu[j];
+    const double t = a.imu[j];
+    if (!isfinite(t)) atomicMin(&a.first[3], static_cast<unsigned long long>(j));
+    a.keys[a.n_gps + j] = t;
     a.vals[a.n_gps + j] = static_cast<int32_t>(a.n_gps + j);
 }
 
@@ -418,7 +422,7 @@ int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* im
     const int64_t nk = n_gps + n_imu;
 
     // one workspace: east, north, keys, keys_sorted (8 B); keep, pos, vals, vals_sorted (4 B);
-    // zone, letter (1 B); first[2], bias[6]; then hipCUB temporaries
+    // zone, letter (1 B); first[4], bias[6]; then hipCUB temporaries
     size_t sort_tmp = 0, scan_tmp = 0;
     KF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (double*)nullptr, (double*)nullptr, (int32_t*)nullptr,
                                               (int32_t*)nullptr, static_cast<int>(nk), 0, 64, st),
@@ -430,7 +434,7 @@ int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* im
     const size_t g8 = al(8 * std::max<int64_t>(n_gps, 1)), k8 = al(8 * std::max<int64_t>(nk, 1));
     const size_t g4 = al(4 * std::max<int64_t>(n_gps, 1)), k4 = al(4 * std::max<int64_t>(nk, 1));
     const size_t g1 = al(std::max<int64_t>(n_gps, 1));
-    const size_t bytes = 2 * g8 + 2 * k8 + 2 * g4 + 2 * k4 + 2 * g1 + al(8 * 8) + al(std::max(sort_tmp, scan_tmp));
+    const size_t bytes = 2 * g8 + 2 * k8 + 2 * g4 + 2 * k4 + 2 * g1 + al(10 * 8) + al(std::max(sort_tmp, scan_tmp));
     DevBuf ws;
     KF_TRY(hipMalloc(&ws.p, bytes), "kf_ingest workspace");
     char* w = static_cast<char*>(ws.p);
@@ -453,11 +457,11 @@ int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* im
     a.zone = reinterpret_cast<int8_t*>(w); w += g1;
     a.letter = w; w += g1;
     a.first = reinterpret_cast<unsigned long long*>(w);
-    a.bias = reinterpret_cast<double*>(w + 16);
-    w += al(8 * 8);
+    a.bias = reinterpret_cast<double*>(w + 32);
+    w += al(10 * 8);
     void* tmp = w;
 
-    const unsigned long long none[2] = {~0ull, ~0ull};
+    const unsigned long long none[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     KF_TRY(hipMemcpyAsync(a.first, none, sizeof none, hipMemcpyHostToDevice, st), "kf_ingest init");
     if (n_gps) {
         fix_kernel<<<grid(n_gps), kIngBlock, 0, st>>>(a);
@@ -483,7 +487,7 @@ int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* im
                                                   static_cast<int>(nk), 0, 64, st),
                "kf_ingest sort");
     }
-    unsigned long long first[2];
+    unsigned long long first[4];
     double bias_out[6];
     int32_t last_pos = 0, last_keep = 0;
     KF_TRY(hipMemcpyAsync(first, a.first, sizeof first, hipMemcpyDeviceToHost, st), "kf_ingest readback");
@@ -496,6 +500,15 @@ int kf_ingest(const double* gps, int64_t n_gps, int64_t ld_gps, const double* im
     if (first[0] == ~0ull)
         return set_error(KF_EINVAL, "kf_ingest: no GPS row has a latitude (compute_imu_biases finds no "
                                     "first valid index, kf_workers.py:336-338)");
+    // a time that is NaN or +-inf has no place in the merge: it would sort level with or past the
+    // dropped fixes' +inf keys, and the first n_fix + n_imu sorted rows would hold a dropped fix
+    // in its stead.  Refused before the gather reads that order (a dropped fix's time is never
+    // looked at, as the reference never parses it).
+    if (first[2] != ~0ull)
+        return set_error(KF_EINVAL, "kf_ingest: GPS row %llu is a kept fix whose time is not finite (NaN or +-inf)",
+                         first[2]);
+    if (first[3] != ~0ull)
+        return set_error(KF_EINVAL, "kf_ingest: IMU row %llu has a time that is not finite (NaN or +-inf)", first[3]);
     const int64_t n_fix = last_pos + last_keep;
     GatherArgs g{};
     g.n_events = n_fix + n_imu;

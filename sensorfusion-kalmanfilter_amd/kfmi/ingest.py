@@ -124,7 +124,8 @@ def ingest_arrays(gps, imu, with_altitude=True, device=0, bias=None):
     """Merged event stream from parsed columns: gps [4, n] (time, latitude, longitude,
     altitude), imu [11, m] (GPS_COLUMNS / IMU_COLUMNS order), NumPy or torch.  bias: optional
     (angular_velocity_bias[3], linear_acceleration_bias[3]) to use instead of the
-    compute_imu_biases means."""
+    compute_imu_biases means.  KFError when no GPS row has a latitude, or when the time of a kept
+    fix or of an IMU row is NaN or +-inf (a dropped fix's time is never looked at)."""
     dev = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
     g = torch.as_tensor(np.ascontiguousarray(gps, dtype=np.float64) if not torch.is_tensor(gps) else gps,
                         dtype=torch.float64).to(dev).contiguous()
